@@ -14,6 +14,10 @@ values, prediction update). The timed region covers exactly K steps between barr
 ``value`` = rows/sec of a 100-tree training = N_total / (100 * ms_per_step / 1000), whole job.
 Multi-GPU (torchrun): rows are sharded over ranks (strong scaling: total rows fixed); per-level
 histograms and leaf sums are all-reduced over RCCL.
+
+A plain run does the headline window only: data, warm-up trees, the K timed trees, the result line.
+``--dump-outputs DIR`` also writes what that fit returned (``dump_outputs``). ``--full`` adds the side
+measurements reported in ``config``: the whole 100-tree job and the AUTO-histogram trees.
 """
 from __future__ import annotations
 
@@ -53,6 +57,35 @@ def make_higgs_like(n: int, seed: int, device) -> tuple:
              + 0.3 * X[3] - 0.35 * (X[25] > 1.2).float() + 0.25 * X[0] * X[5] - 0.3)
     y = (torch.rand(n, generator=g, device=device) < torch.sigmoid(logit)).float()
     return X, y
+
+
+DUMP_ROWS = 1 << 20          # rows of the seeded sample the per-row outputs are written for
+DUMP_METRICS = ("AUC", "pr_auc", "logloss", "MSE", "RMSE", "Gini", "r2", "nobs")
+
+
+def dump_outputs(path: str, model, trainer, X) -> None:
+    """Write what the headline fit handed back after its last timed tree as ``path/<name>.npy`` (float32 / float64,
+    ~21 MB at 11M rows): the forest's node tables, the training margin and the model's predictions on a fixed seeded
+    sample of this rank's rows (all rows when there are at most DUMP_ROWS), and the training metrics. The data
+    and every seed are fixed, so two builds run with the same arguments write comparable files."""
+    os.makedirs(path, exist_ok=True)
+    n = X.shape[1]
+    if n > DUMP_ROWS:
+        idx = np.sort(np.random.default_rng(20240611).choice(n, DUMP_ROWS, replace=False))
+    else:
+        idx = np.arange(n)
+    rows = torch.as_tensor(idx, device=X.device)
+    flat = model.forest.flatten()
+    out = {"forest_" + k: np.asarray(flat[k]).astype(np.float32 if k in ("thr", "value") else np.float64)
+           for k in ("feat", "thr", "left", "right", "na_left", "value", "roots")}
+    out["sample_rows"] = idx.astype(np.float64)
+    out["train_margin"] = trainer.f[rows].float().cpu().numpy()
+    out["predict_proba"] = model.score_tensor(X[:, rows].contiguous()).float().cpu().numpy()
+    tm = model.output["training_metrics"]
+    out["training_metrics"] = np.array([float(tm[k]) if tm.get(k) is not None else np.nan for k in DUMP_METRICS],
+                                       dtype=np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def _free_port() -> int:
@@ -104,10 +137,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--rows", type=int, default=11_000_000)
     ap.add_argument("--depth", type=int, default=6)
-    ap.add_argument("--no-job", action="store_true", help="skip the whole 100-tree job measurement")
-    ap.add_argument("--no-auto", action="store_true", help="skip the AUTO-histogram side measurement")
-    ap.add_argument("--auto-steps", type=int, default=20, help="timed AUTO-histogram trees reported next to the "
-                    "headline (auto_ms_per_tree; H2O's default histogram_type)")
+    ap.add_argument("--full", action="store_true", help="after the headline window also measure the whole 100-tree "
+                    "job and the AUTO-histogram trees (a plain run times the headline window only)")
+    ap.add_argument("--no-job", action="store_true", help="with --full: skip the whole 100-tree job measurement")
+    ap.add_argument("--no-auto", action="store_true", help="with --full: skip the AUTO-histogram side measurement")
+    ap.add_argument("--auto-steps", type=int, default=20, help="with --full: timed AUTO-histogram trees reported next "
+                    "to the headline (auto_ms_per_tree; H2O's default histogram_type)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the headline fit returned after "
+                    "its last timed tree (forest tables, training margin, predictions, training metrics) as "
+                    "DIR/<name>.npy")
     ap.add_argument("--histogram-type", default="QuantilesGlobal",
                     help="H2O histogram_type (the headline config is QuantilesGlobal; AUTO = UniformAdaptive with "
                     "nbins_top_level=1024, H2O's default)")
@@ -191,14 +229,19 @@ def main():
                 times["t1"] = time.perf_counter()
                 times["comm"] = coll.stats()
 
-        model = TimedGBM(params).fit(X, y, None, None, info)
-        return model, max_over_ranks(times["t1"] - times["t0"]), times["comm"], params
+        trainer = TimedGBM(params)
+        model = trainer.fit(X, y, None, None, info)
+        return model, trainer, max_over_ranks(times["t1"] - times["t0"]), times["comm"], params
 
-    model, dt, comm, params = timed_fit(args.histogram_type, args.warmup, args.steps)
+    model, trainer, dt, comm, params = timed_fit(args.histogram_type, args.warmup, args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, trainer, X)
+    del trainer
+    # everything below the headline window runs under --full only
     # the whole 100-tree job as a user runs it (binning, 100 trees, training metrics), untimed by the
     # driver contract but reported next to the per-tree value
     job_ms = None
-    if not args.no_job:
+    if args.full and not args.no_job:
         sync()
         j0 = time.perf_counter()
         GBMTrainer(dict(params, ntrees=100)).fit(X, y, None, None, info)
@@ -206,8 +249,8 @@ def main():
         job_ms = max_over_ranks((time.perf_counter() - j0) * 1000.0)
     # H2O's DEFAULT histogram (AUTO = UniformAdaptive, nbins_top_level 1024) on the same data, same window shape
     auto_ms = None
-    if not args.no_auto and args.histogram_type.lower() != "auto" and args.auto_steps > 0:
-        _, adt, _, _ = timed_fit("AUTO", args.warmup, args.auto_steps)
+    if args.full and not args.no_auto and args.histogram_type.lower() != "auto" and args.auto_steps > 0:
+        _, _, adt, _, _ = timed_fit("AUTO", args.warmup, args.auto_steps)
         auto_ms = adt * 1000.0 / args.auto_steps
     ms_per_step = dt * 1000.0 / args.steps
     rows_per_sec = n_total / (100 * ms_per_step / 1000.0)

@@ -69,8 +69,41 @@ def test_bench_reports_auto_histogram_time():
     env = dict(os.environ, OMP_NUM_THREADS="2")
     env.pop("WORLD_SIZE", None)
     out = subprocess.run([sys.executable, "bench.py", "--device", "cpu", "--rows", "4000", "--steps", "2", "--warmup", "1",
-                          "--no-job", "--auto-steps", "2"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+                          "--full", "--no-job", "--auto-steps", "2"], cwd=ROOT, env=env, capture_output=True, text=True,
+                         timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads([l_ for l_ in out.stdout.splitlines() if l_.startswith("{")][0])
     assert line["config"]["auto_ms_per_tree"] is not None and line["config"]["auto_ms_per_tree"] > 0
     assert line["rccl_world"] == 0
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """Without ``--full`` only the headline window runs (no 100-tree job, no AUTO trees); ``--dump-outputs`` writes
+    the fit's outputs as float .npy files, identical from run to run, and ``--steps`` sets the trees that are built."""
+    import numpy as np
+    env = dict(os.environ, OMP_NUM_THREADS="2")
+    env.pop("WORLD_SIZE", None)
+    dumps = []
+    for d in ("a", "b"):
+        out = subprocess.run([sys.executable, "bench.py", "--device", "cpu", "--rows", "3000", "--steps", "2", "--warmup",
+                              "1", "--dump-outputs", str(tmp_path / d)], cwd=ROOT, env=env, capture_output=True,
+                             text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        line = json.loads([l_ for l_ in out.stdout.splitlines() if l_.startswith("{")][0])
+        assert line["steps"] == 2 and line["ms_per_step"] > 0
+        assert line["value"] == pytest.approx(3000 / (100 * line["ms_per_step"] / 1000.0), rel=1e-3)
+        cfg = line["config"]
+        assert cfg["job_100_trees_ms_incl_binning_and_metrics"] is None and cfg["auto_ms_per_tree"] is None
+        dumps.append({f[:-4]: np.load(tmp_path / d / f) for f in sorted(os.listdir(tmp_path / d))})
+    a, b = dumps
+    assert {"forest_feat", "forest_thr", "forest_value", "forest_roots", "train_margin", "predict_proba",
+            "training_metrics"} <= set(a) and set(a) == set(b)
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert len(a["forest_roots"]) == 3                              # warmup + steps trees, no more
+    assert a["train_margin"].shape == (3000, 1) and a["predict_proba"].shape == (3000, 2)
+    # the model's prediction of its own training rows is the sigmoid of the margin the trainer kept
+    assert np.allclose(a["predict_proba"][:, 1], 1 / (1 + np.exp(-a["train_margin"][:, 0].astype(np.float64))), atol=1e-5)
+    assert a["training_metrics"][0] == pytest.approx(cfg["train_auc_after_all_trees"])
+    for k in a:
+        assert np.array_equal(a[k], b[k], equal_nan=True), k
