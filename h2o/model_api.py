@@ -555,11 +555,18 @@ class ModelBaseAPI:
             fig.savefig(save_plot_path)
         return fig
 
+    def predict_contributions(self, test_data, output_format="Original", top_n=None, bottom_n=None, compare_abs=False):
+        """TreeSHAP contributions (``features..., BiasTerm``), or with ``top_n`` / ``bottom_n`` / ``compare_abs`` the
+        per-row sorted ``top_feature_i, top_value_i, ..., bottom_feature_i, bottom_value_i, ..., BiasTerm`` frame of
+        h2o-py. ``output_format`` ("Original" / "Compact") makes no difference here: nothing is one-hot encoded."""
+        from llama_github_io_amd import explain
+        return explain.predict_contributions(self._m(), test_data, output_format=output_format, top_n=top_n,
+                                             bottom_n=bottom_n, compare_abs=compare_abs)
+
     def fair_shap_plot(self, frame, column, protected_columns, autoscale=True, figsize=None, jitter=0.35, alpha=1,
                        save_plot_path=None):
         """SHAP contribution of ``column`` against its value, coloured by protected group."""
-        m = self._m()
-        contrib = m.predict_contributions(frame)
+        contrib = self.predict_contributions(frame)
         cvals = contrib._col(column).as_float().cpu().numpy()
         xv = frame._col(column).as_float().cpu().numpy()
         pcs = [protected_columns] if isinstance(protected_columns, str) else list(protected_columns)

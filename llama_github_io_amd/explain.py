@@ -2,9 +2,11 @@
 scoreContributions`` (predict_contributions), ``hex/PartialDependence.java`` (partial_plot),
 ``hex/tree/FriedmanPopescusH.java`` (h statistic), ``hex/FeatureInteractions*.java``).
 
-* ``predict_contributions``: exact path-dependent TreeSHAP in the native runtime (``csrc/treeshap.cpp``,
+* ``predict_contributions``: exact path-dependent TreeSHAP; on a CUDA model the path-decomposed HIP kernel
+  of ``ops/shap.py`` / ``csrc/shap_kernels.hip``, else the native runtime (``csrc/treeshap.cpp``,
   one thread per row range) over the flat forest; output columns = features + ``BiasTerm`` in the
-  link (margin) space, summing to the raw prediction (GBM adds init_f, DRF averages trees).
+  link (margin) space, summing to the raw prediction (GBM adds init_f, DRF averages trees), or the
+  sorted ``top_n`` / ``bottom_n`` pairs of h2o-py.
 * ``partial_plot``: for each grid value of a column (equally spaced over [min, max] / levels) the
   column is overwritten on device and the whole frame re-scored (one forest-kernel launch per grid
   point): mean, sd, std err; 2-D pairs, multinomial targets, ICE rows, weights.
@@ -16,6 +18,7 @@ from __future__ import annotations
 
 import ctypes
 import math
+import os
 
 import numpy as np
 import torch
@@ -51,24 +54,78 @@ def tree_shap(forest, X: torch.Tensor, nthreads: int = 0) -> np.ndarray:
     return out
 
 
+def tree_shap_device(forest, X: torch.Tensor) -> torch.Tensor:
+    """X [F, N] -> contributions [N, K, F+1] (float64, margin space, per-tree sums) on X's device, through the
+    path table of ``ops/shap.py``: the HIP kernel for CUDA tensors, its PyTorch reference for CPU tensors. A
+    path needs a lane per element, so a forest whose longest path has more than ``ops.shap.MAX_PATH_LEN`` (64)
+    elements stays on the CPU recursion (:func:`tree_shap`) and only the result is moved to X's device."""
+    from .ops import shap
+    paths = shap.forest_paths(forest)
+    if paths.max_len > shap.MAX_PATH_LEN:
+        return torch.from_numpy(tree_shap(forest, X)).to(X.device)
+    return shap.path_shap(paths, X, forest.K)
+
+
+def _sorted_contributions(c: torch.Tensor, names, top_n, bottom_n, compare_abs):
+    """h2o-py ``top_n`` / ``bottom_n`` / ``compare_abs``: per row the feature contributions sorted descending (by
+    magnitude with ``compare_abs``), as ``top_feature_i, top_value_i`` pairs, then ``bottom_*`` pairs (smallest
+    first), then ``BiasTerm``. A negative count, ``top_n + bottom_n >= F``, or ``compare_abs`` with neither count,
+    returns every feature as ``top_*``."""
+    F = len(names)
+    top, bot = int(top_n or 0), int(bottom_n or 0)
+    if top < 0 or bot < 0 or top + bot >= F or top + bot == 0:      # compare_abs alone: everything, by magnitude
+        top, bot = F, 0
+    phi = c[:, :F]
+    order = torch.sort(phi.abs() if compare_abs else phi, dim=1, descending=True, stable=True).indices
+    vals = torch.gather(phi, 1, order)
+    cols = []
+    for kind, n, pos in (("top", top, lambda i: i), ("bottom", bot, lambda i: F - 1 - i)):
+        for i in range(n):
+            cols.append(Column(f"{kind}_feature_{i + 1}", "enum", order[:, pos(i)].to(torch.int32), list(names)))
+            cols.append(Column(f"{kind}_value_{i + 1}", "real", vals[:, pos(i)].contiguous()))
+    cols.append(Column("BiasTerm", "real", c[:, F].contiguous()))
+    return H2OFrame._from_columns(cols)
+
+
 def predict_contributions(model, frame, output_format="Original", top_n=None, bottom_n=None, compare_abs=False):
+    """TreeSHAP contributions of every row, in the margin space: ``features..., BiasTerm``.
+
+    A model on a CUDA device is explained on that device (model matrix, ``ops/shap.py`` path kernel, DRF
+    averaging and ``init_f``; the columns are float64 CUDA tensors) unless ``H2O_SHAP_HIP=0``; otherwise the
+    host recursion of ``csrc/treeshap.cpp`` runs. ``top_n`` / ``bottom_n`` / ``compare_abs`` follow h2o-py
+    (:func:`_sorted_contributions`). ``output_format`` is ``"Original"`` or ``"Compact"``: the two differ in the
+    reference only for one-hot encoded XGBoost models, and this engine never one-hot encodes, so they are
+    identical here."""
     m = getattr(model, "_model", model)
     if not hasattr(m, "forest") or m.forest is None:
         raise NotImplementedError("predict_contributions is available for tree models (GBM, DRF, XGBoost)")
-    X, _ = frame.model_matrix(m.info, device=torch.device("cpu"))
-    phi = tree_shap(m.forest, X)
-    if m.model_category == "Multinomial":
-        raise NotImplementedError("contributions for multinomial models are not supported (as in H2O)")
-    c = phi[:, 0, :]
-    if m.algo == "drf":
-        c = c / max(1, m.ntrees_built())
-        if m.model_category == "Binomial" and not m.output.get("double_trees"):
-            pass
+    if str(output_format).lower() not in ("original", "compact"):
+        raise ValueError(f"output_format must be 'Original' or 'Compact', got {output_format!r}")
     init = getattr(m, "init_f", 0.0)
     init = init[0] if isinstance(init, (list, tuple)) else init
-    c[:, -1] += float(init or 0.0)
+    dev = torch.device(getattr(m, "device", None) or "cpu")
+    if dev.type == "cuda" and os.environ.get("H2O_SHAP_HIP", "1") != "0":
+        if m.model_category == "Multinomial":
+            raise NotImplementedError("contributions for multinomial models are not supported (as in H2O)")
+        X, _ = frame.model_matrix(m.info, device=dev)
+        c = tree_shap_device(m.forest, X)[:, 0, :]
+        if m.algo == "drf":
+            c = c / max(1, m.ntrees_built())
+        c[:, -1] += float(init or 0.0)
+    else:
+        X, _ = frame.model_matrix(m.info, device=torch.device("cpu"))
+        phi = tree_shap(m.forest, X)
+        if m.model_category == "Multinomial":
+            raise NotImplementedError("contributions for multinomial models are not supported (as in H2O)")
+        c = phi[:, 0, :]
+        if m.algo == "drf":
+            c = c / max(1, m.ntrees_built())
+        c[:, -1] += float(init or 0.0)
+        c = torch.as_tensor(c)
+    if top_n or bottom_n or compare_abs:
+        return _sorted_contributions(c, list(m.info.x), top_n, bottom_n, compare_abs)
     names = list(m.info.x) + ["BiasTerm"]
-    cols = [Column(n, "real", torch.as_tensor(c[:, i])) for i, n in enumerate(names)]
+    cols = [Column(n, "real", c[:, i]) for i, n in enumerate(names)]
     return H2OFrame._from_columns(cols)
 
 

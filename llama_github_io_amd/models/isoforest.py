@@ -127,7 +127,7 @@ class IsolationForestTrainer(SharedTreeTrainer):
                     depth[tree.left[i]] = depth[i] + 1
                     depth[tree.right[i]] = depth[i] + 1
             tree.value = np.where(tree.feat < 0, depth, 0).astype(np.float32)
-        model.forest._flat.clear()
+        model.forest.invalidate()
         s = model.forest.predict_raw(self.X)[:, 0]
         mn, mx = float(s.min()), float(s.max())
         if coll.is_dist():

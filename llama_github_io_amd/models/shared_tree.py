@@ -102,7 +102,7 @@ class SharedTreeModel(Model):
             if warn is None and (cover == 0).any():
                 warn = (t, self.forest.tree_class[t])
             tree.cover = cover.astype(tree.cover.dtype if hasattr(tree.cover, "dtype") else np.float64)
-        self.forest._flat = {}
+        self.forest.invalidate()
         if warn is not None:
             return (f"Some of the updated nodes have zero weights (eg.: tree #{warn[0] + 1}, "
                     f"class #{warn[1] + 1}).")

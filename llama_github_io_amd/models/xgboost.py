@@ -384,7 +384,7 @@ class XGBoostTrainer(SharedTreeTrainer):
                 it = i // self.K
                 if it < len(self.tree_w):
                     tree.value = (tree.value * self.tree_w[it]).astype(np.float32)
-            model.forest._flat.clear()
+            model.forest.invalidate()
 
     def _training_metrics(self, model):
         self._flush_pending()

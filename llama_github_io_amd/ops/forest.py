@@ -149,6 +149,12 @@ class Forest:
         self.tree_class = list(tree_class or [0] * len(self._trees))
         self.K = n_classes_out
         self._flat = {}
+        self._paths = {}            # TreeSHAP path table (ops/shap.py), dropped together with ``_flat``
+
+    def invalidate(self):
+        """Drop everything derived from the node tables (flat device arrays, TreeSHAP path table)."""
+        self._flat.clear()
+        self.__dict__.setdefault("_paths", {}).clear()
 
     @property
     def trees(self):
@@ -170,12 +176,12 @@ class Forest:
             self.trees    # keep insertion order
         self._trees.append(tree)
         self.tree_class.append(cls)
-        self._flat.clear()
+        self.invalidate()
 
     def add_levels(self, tl, binning, cls: int = 0):
         self._pending.append((tl, binning))
         self.tree_class.append(cls)
-        self._flat.clear()
+        self.invalidate()
 
     def depth_leaves(self) -> list:
         """(depth, leaf count) of every tree; trees still pending as level records are read from those records

@@ -1,0 +1,290 @@
+"""Path-decomposed TreeSHAP (formulation: Mitchell, Frank, Holmes, "GPUTreeShap: massively parallel
+exact calculation of SHAP scores for tree ensembles", 2020; recursion being replaced: ``csrc/treeshap.cpp``).
+
+:func:`forest_paths` turns a :class:`~.forest.Forest` into a flat table of root-to-leaf paths, once per
+forest on the host. A path is one leaf and has one element per DISTINCT feature on the way down:
+
+* ``zero_fraction``: product of ``cover[child] / cover[node]`` over the path's splits on that feature;
+* the merged condition that tells whether a row follows the path at that feature: numeric splits
+  intersect to an interval ``lo <= x < hi`` (``x >= thr`` goes right, so ``lo`` is the largest threshold
+  passed on the right and ``hi`` the smallest passed on the left; an element with no left split has no
+  upper bound and accepts ``+inf``), categorical splits AND their level bitsets (complemented within the
+  split's ``cat_nbits`` when the path goes right; codes past a split's ``cat_nbits`` take that split's NA
+  direction);
+* ``na_ok``: NaN (or a code < 0 / >= the merged width) follows the path only if every split on the
+  feature sends NA toward it.
+
+Element 0 of every path is the dummy root (``feature = -1``, both fractions 1); a single-leaf tree is a
+path of that element alone. The bias column is ``sum(value * prod(zero_fraction))`` per class, in fp64.
+
+:func:`path_shap` evaluates the table: CUDA tensors run the HIP kernel ``k_tree_shap``
+(``csrc/shap_kernels.hip``), CPU tensors a vectorised PyTorch evaluation of the same table (the CPU
+suite's check of the decomposition). A path needs one lane per element, so forests whose longest path has
+more than :data:`MAX_PATH_LEN` (64) elements are not evaluated here: :func:`path_shap` raises for them and
+``explain.tree_shap_device`` keeps them on the CPU recursion.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass, field
+
+import numpy as np
+import torch
+
+from . import _native as nat
+
+c_int, c_ll, c_void_p = nat.c_int, nat.c_ll, nat.c_void_p
+
+nat.register_hip_signatures({
+    # X, N, F, K, G, P, feat, zf, lo, hi, flags, cat_off, cat_nbits, cat_bits, len, value, cls, rounds, out, stream
+    "h2o_tree_shap": [c_void_p, c_ll, c_int, c_int, c_int, c_int] + [c_void_p] * 11 + [c_int, c_void_p, c_void_p],
+})
+
+MAX_PATH_LEN = 64       # one wave lane per path element
+ROW_TILE = 64           # rows per block of k_tree_shap (SHAP_R in csrc/shap_kernels.hip)
+X_TILE_BYTES = 16384    # the block stages X in LDS when F * ROW_TILE * 4 fits (SHAP_X_BYTES)
+PHI_TILE_BYTES = 32768  # ... and accumulates phi in LDS when ROW_TILE * K * (F+1) * 8 fits (SHAP_PHI_BYTES)
+
+NA_OK, IS_CAT, HAS_HI = 1, 2, 4
+
+
+@dataclass
+class PathTable:
+    """Paths padded to ``G`` elements, row-major ``[P, G]`` element arrays and ``[P]`` path arrays."""
+    G: int
+    max_len: int
+    n_features: int                 # 1 + largest feature index used by any split
+    K: int
+    feat: np.ndarray                # int32 [P, G], -1 = dummy root / padding
+    zf: np.ndarray                  # float64 [P, G]
+    lo: np.ndarray                  # float32 [P, G]
+    hi: np.ndarray                  # float32 [P, G]
+    flags: np.ndarray               # int32 [P, G]: NA_OK | IS_CAT | HAS_HI
+    cat_off: np.ndarray             # int32 [P, G] word offset into cat_bits
+    cat_nbits: np.ndarray           # int32 [P, G]
+    cat_bits: np.ndarray            # uint32 words
+    len: np.ndarray                 # int32 [P] elements of the path (dummy included)
+    value: np.ndarray               # float64 [P]
+    cls: np.ndarray                 # int32 [P]
+    tree: np.ndarray                # int32 [P]
+    bias: np.ndarray                # float64 [K]
+    _dev: dict = field(default_factory=dict, repr=False)
+
+    @property
+    def n_paths(self) -> int:
+        return int(self.len.shape[0])
+
+    def on(self, device) -> dict:
+        key = str(device)
+        if key not in self._dev:
+            names = ("feat", "zf", "lo", "hi", "flags", "cat_off", "cat_nbits", "cat_bits", "len", "value", "cls", "bias")
+            d = {}
+            for n in names:
+                a = np.ascontiguousarray(getattr(self, n))
+                if a.dtype == np.uint32:
+                    a = a.view(np.int32)
+                d[n] = torch.from_numpy(a).to(device)
+            self._dev[key] = d
+        return self._dev[key]
+
+
+class _Elem:
+    __slots__ = ("feature", "zf", "cat", "lo", "hi", "has_hi", "na_ok", "mask", "nbits")
+
+    def copy(self):
+        e = _Elem()
+        for s in self.__slots__:
+            setattr(e, s, getattr(self, s))
+        return e
+
+
+def _merge(e: _Elem | None, f: int, frac: float, is_cat: bool, thr: float, bits: int, nbits: int, na_left: bool,
+           go_left: bool) -> _Elem:
+    """AND one split (taken toward ``go_left``) into the path's element of feature ``f``."""
+    toward = na_left if go_left else not na_left
+    if e is None:
+        e = _Elem()
+        e.feature, e.zf, e.cat = f, 1.0, is_cat
+        e.lo, e.hi, e.has_hi, e.na_ok = float("-inf"), float("inf"), False, True
+        e.mask, e.nbits = 0, 0                        # zero-width bitset: every code takes the NA side
+    else:
+        e = e.copy()
+        if e.cat != is_cat:
+            raise ValueError(f"feature {f} is split both as numeric and as categorical")
+    e.zf *= frac
+    was_ok, e.na_ok = e.na_ok, e.na_ok and toward
+    if is_cat:
+        full = (1 << nbits) - 1
+        m = bits & full if go_left else ~bits & full
+        w = max(e.nbits, nbits)
+        # codes past a split's own width take that split's NA direction
+        if toward and nbits < w:
+            m |= ((1 << w) - 1) ^ full
+        old = e.mask
+        if was_ok and e.nbits < w:
+            old |= ((1 << w) - 1) ^ ((1 << e.nbits) - 1)
+        e.mask, e.nbits = old & m, w
+    elif go_left:
+        # x < thr; a NaN threshold sends every value right, so nothing goes left
+        t = float("-inf") if thr != thr else thr
+        e.hi, e.has_hi = (min(e.hi, t) if e.has_hi else t), True
+    elif thr == thr:
+        e.lo = max(e.lo, thr)
+    return e
+
+
+def forest_paths(forest) -> PathTable:
+    """Path table of ``forest`` (cached on it; dropped with the flat arrays when the forest changes)."""
+    cache = forest.__dict__.setdefault("_paths", {})
+    if "table" in cache:
+        return cache["table"]
+    fl = forest.flatten()
+    cover = np.concatenate([t.cover.astype(np.float64) for t in forest.trees]) if forest.trees else np.zeros(0)
+    feat, thr, left, right = fl["feat"].tolist(), fl["thr"].astype(np.float64).tolist(), fl["left"].tolist(), fl["right"].tolist()
+    nal, coff, cnb = fl["na_left"].tolist(), fl["cat_off"].tolist(), fl["cat_nbits"].tolist()
+    words, val, cov = fl["cat_bits"], fl["value"].astype(np.float64).tolist(), cover.tolist()
+    paths = []          # (tree, cls, value, [elements])
+    for ti, (root, cls) in enumerate(zip(fl["roots"].tolist(), fl["cls"].tolist())):
+        stack = [(root, {})]
+        while stack:
+            n, els = stack.pop()
+            f = feat[n]
+            if f < 0:
+                paths.append((ti, cls, val[n], list(els.values())))
+                continue
+            cn = cov[n] if cov[n] > 0 else 1.0
+            is_cat = coff[n] >= 0
+            bits = 0
+            if is_cat:
+                nw = (cnb[n] + 31) >> 5
+                for k, wd in enumerate(words[coff[n]:coff[n] + nw].tolist()):
+                    bits |= int(wd) << (32 * k)
+            for child, go_left in ((left[n], True), (right[n], False)):
+                nxt = dict(els)
+                nxt[f] = _merge(els.get(f), f, cov[child] / cn, is_cat, thr[n], bits, cnb[n], bool(nal[n]), go_left)
+                stack.append((child, nxt))
+    P = len(paths)
+    max_len = 1 + max((len(p[3]) for p in paths), default=0)
+    G = next((g for g in (8, 16, 32, 64) if g >= max_len), max_len)
+    shape = (P, G)
+    t = PathTable(G=G, max_len=max_len, n_features=0, K=int(forest.K),
+                  feat=np.full(shape, -1, np.int32), zf=np.ones(shape, np.float64),
+                  lo=np.full(shape, -np.inf, np.float32), hi=np.full(shape, np.inf, np.float32),
+                  flags=np.full(shape, NA_OK, np.int32), cat_off=np.zeros(shape, np.int32),
+                  cat_nbits=np.zeros(shape, np.int32), cat_bits=np.zeros(1, np.uint32),
+                  len=np.ones(P, np.int32), value=np.zeros(P, np.float64), cls=np.zeros(P, np.int32),
+                  tree=np.zeros(P, np.int32), bias=np.zeros(max(int(forest.K), 1), np.float64))
+    cat_words = []
+    nw_total = 0
+    for p, (ti, cls, v, els) in enumerate(paths):
+        t.tree[p], t.cls[p], t.value[p], t.len[p] = ti, cls, v, 1 + len(els)
+        w = v
+        for j, e in enumerate(els, start=1):
+            t.feat[p, j], t.zf[p, j] = e.feature, e.zf
+            w *= e.zf
+            fg = NA_OK if e.na_ok else 0
+            if e.cat:
+                nw = max(1, (e.nbits + 31) >> 5)
+                cat_words.extend((e.mask >> (32 * k)) & 0xFFFFFFFF for k in range(nw))
+                t.cat_off[p, j], t.cat_nbits[p, j] = nw_total, e.nbits
+                nw_total += nw
+                fg |= IS_CAT
+            else:
+                t.lo[p, j] = e.lo
+                if e.has_hi:
+                    t.hi[p, j] = e.hi
+                    fg |= HAS_HI
+            t.flags[p, j] = fg
+        t.bias[cls] += w
+    if cat_words:
+        t.cat_bits = np.asarray(cat_words, dtype=np.uint32)
+    t.n_features = int(t.feat.max()) + 1 if P else 0
+    cache["table"] = t
+    return t
+
+
+def path_shap(paths: PathTable, X: torch.Tensor, K: int, rounds: int = 0, out: torch.Tensor | None = None) -> torch.Tensor:
+    """X: float32 ``[F, N]`` column-major model matrix -> contributions ``[N, K, F+1]`` float64 on X's
+    device (margin space, per-tree sums, last column = bias). ``rounds`` > 0 fixes how many groups of
+    paths one block of the kernel walks (0: chosen from the grid size). ``out``: a contiguous float64
+    ``[>= N, K, F+1]`` tensor on X's device to accumulate into (its first N rows) instead of a new one."""
+    if paths.max_len > MAX_PATH_LEN:
+        raise ValueError(f"longest path has {paths.max_len} elements, more than the {MAX_PATH_LEN} lanes of a wave")
+    F, N = X.shape
+    if paths.n_features > F:
+        raise ValueError(f"the forest splits on feature {paths.n_features - 1}, X has {F} rows")
+    if int(paths.cls.max(initial=0)) >= K:
+        raise ValueError("a tree's class is outside [0, K)")
+    if out is None:
+        out = torch.zeros(N, K, F + 1, dtype=torch.float64, device=X.device)
+    elif (out.dtype != torch.float64 or out.device != X.device or not out.is_contiguous() or out.dim() != 3
+          or out.shape[0] < N or tuple(out.shape[1:]) != (K, F + 1)):
+        raise ValueError(f"out must be a contiguous float64 [>= {N}, {K}, {F + 1}] tensor on {X.device}")
+    if N == 0:
+        return out
+    Xc = X.contiguous().float()
+    d = paths.on(X.device)
+    if paths.n_paths:
+        if X.is_cuda:
+            nat.call("h2o_tree_shap", Xc.data_ptr(), N, F, K, paths.G, paths.n_paths, d["feat"].data_ptr(),
+                     d["zf"].data_ptr(), d["lo"].data_ptr(), d["hi"].data_ptr(), d["flags"].data_ptr(),
+                     d["cat_off"].data_ptr(), d["cat_nbits"].data_ptr(), d["cat_bits"].data_ptr(), d["len"].data_ptr(),
+                     d["value"].data_ptr(), d["cls"].data_ptr(), int(rounds), out.data_ptr(), nat.stream_ptr(X.device))
+        else:
+            _path_shap_torch(d, paths.G, Xc, K, out[:N])
+    out[:N, :paths.bias.shape[0], F] += d["bias"][:K]
+    return out
+
+
+def _path_shap_torch(d: dict, G: int, X: torch.Tensor, K: int, out: torch.Tensor) -> None:
+    """The kernel's arithmetic, vectorised over (rows, paths, elements): EXTEND builds the permutation
+    weights of every path, UNWOUND_SUM removes each element in turn."""
+    F, N = X.shape
+    P = d["len"].shape[0]
+    feat, zf, ln = d["feat"].long(), d["zf"], d["len"].long()
+    flags, cnb, coff, bits = d["flags"], d["cat_nbits"].long(), d["cat_off"].long(), d["cat_bits"].long() & 0xFFFFFFFF
+    na_ok, is_cat, has_hi = (flags & NA_OK) != 0, (flags & IS_CAT) != 0, (flags & HAS_HI) != 0
+    e = torch.arange(G)
+    real = (e[None, :] >= 1) & (e[None, :] < ln[:, None])           # [P, G]
+    fidx = feat.clamp(min=0)
+    dst = (d["cls"].long()[:, None] * (F + 1) + fidx).reshape(1, -1)
+    rcp = torch.zeros(G + 2, dtype=torch.float64)
+    rcp[1:] = 1.0 / torch.arange(1, G + 2, dtype=torch.float64)
+    dl = (ln - 1)                                                       # index of the last element
+    max_len = int(ln.max())
+    step = max(1, (1 << 21) // max(1, P * G))
+    o2 = out.view(N, K * (F + 1))
+    for r0 in range(0, N, step):
+        x = X[:, r0:r0 + step].T[:, fidx]                               # [n, P, G]
+        n = x.shape[0]
+        isnan = torch.isnan(x)
+        code = torch.nan_to_num(x, nan=-1.0, posinf=-1.0, neginf=-1.0).clamp(-1.0, 2.0 ** 30).long()
+        inr = (code >= 0) & (code < cnb)
+        cs = torch.where(inr, code, torch.zeros_like(code))
+        word = bits[(coff + (cs >> 5)).clamp(max=bits.numel() - 1)]
+        catok = torch.where(inr, ((word >> (cs & 31)) & 1) != 0, na_ok)
+        numok = (x >= d["lo"]) & (~has_hi | (x < d["hi"]))
+        ok = torch.where(isnan, na_ok, torch.where(is_cat, catok, numok))
+        of = torch.where(real, ok, torch.ones_like(ok)).double()          # dummy and padding: 1
+        pw = torch.zeros(n, P, G, dtype=torch.float64)
+        pw[:, :, 0] = 1.0
+        for dd in range(1, max_len):
+            lft = torch.zeros_like(pw)
+            lft[:, :, 1:] = pw[:, :, :-1]
+            new = pw * zf[:, dd:dd + 1] * ((dd - e).double() * rcp[dd + 1]) + of[:, :, dd:dd + 1] * lft * (e.double() * rcp[dd + 1])
+            pw = torch.where((dd < ln)[None, :, None], new, pw)
+        nxt = torch.gather(pw, 2, dl[None, :, None].expand(n, P, 1)).expand(n, P, G).clone()
+        tot = torch.zeros_like(pw)
+        c1 = (dl + 1).double()[None, :, None]
+        c2 = zf * rcp[dl + 1][:, None]
+        c3 = c1 / zf
+        hot = of != 0
+        for i in range(max_len - 2, -1, -1):
+            pi = pw[:, :, i:i + 1]
+            act = (i < dl)[None, :, None]
+            tmp = nxt * c1 * rcp[i + 1]
+            k = (dl - i).clamp(min=0)
+            cold = pi * c3 * rcp[k][None, :, None]
+            tot = torch.where(act, tot + torch.where(hot, tmp, cold), tot)
+            nxt = torch.where(act & hot, pi - tmp * c2 * k.double()[None, :, None], nxt)
+        contrib = torch.where(real, tot * (of - zf) * d["value"][None, :, None], torch.zeros_like(tot))
+        o2[r0:r0 + n].scatter_add_(1, dst.expand(n, -1), contrib.reshape(n, -1))
