@@ -168,20 +168,23 @@ def model_correlation_heatmap(models, frame, top_n=None, cluster_models=True, tr
 
 
 # ------------------------------------------------------------------------------------------------ SHAP
-def _contributions(m, frame, rows=None):
+def _contributions(m, frame, rows=None, background_frame=None):
+    """Contributions of ``rows`` of ``frame``; with a ``background_frame`` baseline SHAP averaged over its rows."""
     sub = frame if rows is None else frame._rows(__import__("torch").as_tensor(rows))
-    return m.predict_contributions(sub).as_data_frame()
+    if background_frame is None:
+        return m.predict_contributions(sub).as_data_frame()
+    return m.predict_contributions(sub, background_frame=background_frame).as_data_frame()
 
 
 def shap_summary_plot(model, frame, columns=None, top_n_features=20, samples=1000, colorize_factors=True, alpha=1,
-                      colormap=None, figsize=(12, 12), jitter=0.35, save_plot_path=None):
+                      colormap=None, figsize=(12, 12), jitter=0.35, save_plot_path=None, background_frame=None):
     """TreeSHAP contributions of up to ``samples`` rows, long format (feature, contribution, normalized
     feature value), features ordered by mean |contribution|."""
     m = _model(model)
     n = frame.nrows
     rng = np.random.default_rng(42)
     rows = np.sort(rng.choice(n, min(samples, n), replace=False)) if n > samples else np.arange(n)
-    c = _contributions(m, frame, rows)
+    c = _contributions(m, frame, rows, background_frame)
     feats = [f for f in c.columns if f != "BiasTerm"]
     if columns:
         feats = [f for f in feats if f in columns]
@@ -213,9 +216,9 @@ def shap_summary_plot(model, frame, columns=None, top_n_features=20, samples=100
 
 
 def shap_explain_row_plot(model, frame, row_index, columns=None, top_n_features=10, figsize=(16, 9),
-                          plot_type="barplot", contribution_type="both", save_plot_path=None):
+                          plot_type="barplot", contribution_type="both", save_plot_path=None, background_frame=None):
     m = _model(model)
-    c = _contributions(m, frame, [int(row_index)]).iloc[0]
+    c = _contributions(m, frame, [int(row_index)], background_frame).iloc[0]
     bias = float(c.get("BiasTerm", 0.0))
     c = c.drop(labels=["BiasTerm"], errors="ignore")
     if columns:
@@ -465,7 +468,7 @@ def explain(models, frame, columns=None, top_n_features=5, include_explanations=
             out["varimp"] = Explanation("varimp", pd.DataFrame(vi, columns=["variable", "relative_importance",
                                                                               "scaled_importance", "percentage"]))
         if _want("shap_summary", include_explanations, exclude_explanations) and _is_tree(m):
-            out["shap_summary"] = shap_summary_plot(m, frame)
+            out["shap_summary"] = shap_summary_plot(m, frame, background_frame=background_frame)
         if _want("pdp", include_explanations, exclude_explanations):
             out["pdp"] = {c: pd_plot(m, frame, c) for c in cols}
         if _want("ice", include_explanations, exclude_explanations) and m.model_category in ("Regression", "Binomial"):
@@ -496,7 +499,7 @@ def explain_row(models, frame, row_index, columns=None, top_n_features=5, includ
     cols = list(columns) if columns else [r[0] for r in vi[:top_n_features]]
     if len(ms) == 1:
         if _want("shap_explain_row", include_explanations, exclude_explanations) and _is_tree(m):
-            out["shap_explain_row"] = shap_explain_row_plot(m, frame, row_index)
+            out["shap_explain_row"] = shap_explain_row_plot(m, frame, row_index, background_frame=background_frame)
         if _want("ice", include_explanations, exclude_explanations):
             out["ice"] = {c: pd_plot(m, frame, c, row_index=row_index) for c in cols}
         return out

@@ -555,13 +555,18 @@ class ModelBaseAPI:
             fig.savefig(save_plot_path)
         return fig
 
-    def predict_contributions(self, test_data, output_format="Original", top_n=None, bottom_n=None, compare_abs=False):
+    def predict_contributions(self, test_data, output_format="Original", top_n=None, bottom_n=None, compare_abs=False,
+                              background_frame=None, output_space=False, output_per_reference=False):
         """TreeSHAP contributions (``features..., BiasTerm``), or with ``top_n`` / ``bottom_n`` / ``compare_abs`` the
         per-row sorted ``top_feature_i, top_value_i, ..., bottom_feature_i, bottom_value_i, ..., BiasTerm`` frame of
-        h2o-py. ``output_format`` ("Original" / "Compact") makes no difference here: nothing is one-hot encoded."""
+        h2o-py. ``output_format`` ("Original" / "Compact") makes no difference here: nothing is one-hot encoded.
+        With ``background_frame``: baseline SHAP against its rows, averaged or (``output_per_reference``) one row per
+        (row, background row) with ``RowIdx`` / ``BackgroundRowIdx``; ``output_space`` makes rows sum to the prediction."""
         from llama_github_io_amd import explain
         return explain.predict_contributions(self._m(), test_data, output_format=output_format, top_n=top_n,
-                                             bottom_n=bottom_n, compare_abs=compare_abs)
+                                             bottom_n=bottom_n, compare_abs=compare_abs,
+                                             background_frame=background_frame, output_space=output_space,
+                                             output_per_reference=output_per_reference)
 
     def fair_shap_plot(self, frame, column, protected_columns, autoscale=True, figsize=None, jitter=0.35, alpha=1,
                        save_plot_path=None):

@@ -6,7 +6,9 @@ scoreContributions`` (predict_contributions), ``hex/PartialDependence.java`` (pa
   of ``ops/shap.py`` / ``csrc/shap_kernels.hip``, else the native runtime (``csrc/treeshap.cpp``,
   one thread per row range) over the flat forest; output columns = features + ``BiasTerm`` in the
   link (margin) space, summing to the raw prediction (GBM adds init_f, DRF averages trees), or the
-  sorted ``top_n`` / ``bottom_n`` pairs of h2o-py.
+  sorted ``top_n`` / ``bottom_n`` pairs of h2o-py. With a ``background_frame``: baseline (interventional) SHAP
+  against its rows (``csrc/shap_baseline_kernels.hip`` on a CUDA model), averaged or per reference, in the margin
+  or the output space.
 * ``partial_plot``: for each grid value of a column (equally spaced over [min, max] / levels) the
   column is overwritten on device and the whole frame re-scored (one forest-kernel launch per grid
   point): mean, sd, std err; 2-D pairs, multinomial targets, ICE rows, weights.
@@ -87,7 +89,103 @@ def _sorted_contributions(c: torch.Tensor, names, top_n, bottom_n, compare_abs):
     return H2OFrame._from_columns(cols)
 
 
-def predict_contributions(model, frame, output_format="Original", top_n=None, bottom_n=None, compare_abs=False):
+def _margin_linkinv(m):
+    """What the model applies to its margin when scoring, as a tensor function; None when it applies nothing
+    (identity links, DRF), so that output-space contributions equal the margin-space ones."""
+    if m.algo == "gbm":
+        d = m.distribution
+        if d.name in ("bernoulli", "quasibinomial", "modified_huber"):
+            return torch.sigmoid
+        if d.link == "identity":
+            return None
+        if d.name == "custom":
+            raise NotImplementedError("output_space is not available for a custom distribution")
+        return d.linkinv
+    if m.algo == "xgboost":
+        d = m.output.get("distribution")
+        if d == "bernoulli":
+            return torch.sigmoid
+        if d in ("poisson", "gamma", "tweedie"):
+            return torch.exp
+    return None
+
+
+def _to_output_space(c: torch.Tensor, linkinv) -> torch.Tensor:
+    """In place, per row of ``c`` (one (row, background row) pair: features..., bias): the feature cells are scaled
+    so that they sum to ``linkinv(f(x)) - linkinv(f(b))`` and the bias becomes ``linkinv(f(b))``. Where the
+    features sum to (almost) nothing the scale is the slope of ``linkinv`` at ``f(b)``."""
+    F = c.shape[1] - 1
+    d = c[:, :F].sum(1)
+    fb = c[:, F].clone()
+    h = 1e-6
+    flat = d.abs() < 1e-12
+    secant = (linkinv(fb + d) - linkinv(fb)) / torch.where(flat, torch.ones_like(d), d)
+    slope = (linkinv(fb + h) - linkinv(fb - h)) / (2 * h)
+    c[:, :F] *= torch.where(flat, slope, secant)[:, None]
+    c[:, F] = linkinv(fb)
+    return c
+
+
+def _baseline_contributions(m, frame, background_frame, output_space, per_reference, top_n, bottom_n, compare_abs):
+    """Baseline SHAP of ``frame`` against ``background_frame`` (``ops/shap.py`` :func:`path_shap_baseline`): the mean
+    over the background rows, or one row per (row, background row)."""
+    from .ops import shap
+    if m.model_category == "Multinomial":
+        raise NotImplementedError("contributions for multinomial models are not supported (as in H2O)")
+    dev = torch.device(getattr(m, "device", None) or "cpu")
+    if dev.type != "cuda" or os.environ.get("H2O_SHAP_HIP", "1") == "0":
+        dev = torch.device("cpu")
+    X, _ = frame.model_matrix(m.info, device=dev)
+    Bg, _ = background_frame.model_matrix(m.info, device=dev)
+    N, B, F = int(X.shape[1]), int(Bg.shape[1]), int(X.shape[0])
+    if B == 0:
+        raise ValueError("background_frame has no rows")
+    limit = int(os.environ.get("H2O_SHAP_MAX_OUT_BYTES", 8 << 30))
+    if per_reference and N * B * (F + 3) * 8 > limit:
+        raise ValueError(f"output_per_reference: {N} rows x {B} background rows x {F + 3} columns of 8 bytes exceed "
+                         f"H2O_SHAP_MAX_OUT_BYTES = {limit}")
+    paths = shap.forest_paths(m.forest)
+    K = m.forest.K
+    scale = 1.0 / max(1, m.ntrees_built()) if m.algo == "drf" else 1.0
+    init = getattr(m, "init_f", 0.0)
+    init = float((init[0] if isinstance(init, (list, tuple)) else init) or 0.0)
+    linkinv = _margin_linkinv(m) if output_space else None
+
+    def pairs(Bc):
+        """[N * b, F+1]: every pair of a row with a background row of Bc, DRF average and init_f applied."""
+        c = shap.path_shap_baseline(paths, X, Bc, K, per_reference=True)[:, 0, :]
+        if scale != 1.0:
+            c = c * scale
+        c[:, -1] += init
+        return _to_output_space(c, linkinv) if linkinv is not None else c
+
+    if per_reference:
+        c = pairs(Bg)
+    elif linkinv is None:
+        c = shap.path_shap_baseline(paths, X, Bg, K)[:, 0, :] * (scale / B)
+        c[:, -1] += init
+    else:
+        # the link is applied per pair: per-reference values of a background chunk in a bounded temporary
+        step = max(1, min(B, (256 << 20) // max(1, N * (F + 1) * 8)))
+        c = torch.zeros(N, F + 1, dtype=torch.float64, device=dev)
+        for b0 in range(0, B, step):
+            c += pairs(Bg[:, b0:b0 + step]).view(N, -1, F + 1).sum(1)
+        c /= B
+    names = list(m.info.x)
+    if top_n or bottom_n or compare_abs:
+        out = _sorted_contributions(c, names, top_n, bottom_n, compare_abs)
+        cols = [out._col(n) for n in out.names]
+    else:
+        cols = [Column(n, "real", c[:, i]) for i, n in enumerate(names + ["BiasTerm"])]
+    if per_reference:
+        pair = torch.arange(N * B, device=dev)
+        cols.append(Column("RowIdx", "int", torch.div(pair, B, rounding_mode="floor").double()))
+        cols.append(Column("BackgroundRowIdx", "int", (pair % B).double()))
+    return H2OFrame._from_columns(cols)
+
+
+def predict_contributions(model, frame, output_format="Original", top_n=None, bottom_n=None, compare_abs=False,
+                          background_frame=None, output_space=False, output_per_reference=False):
     """TreeSHAP contributions of every row, in the margin space: ``features..., BiasTerm``.
 
     A model on a CUDA device is explained on that device (model matrix, ``ops/shap.py`` path kernel, DRF
@@ -95,12 +193,27 @@ def predict_contributions(model, frame, output_format="Original", top_n=None, bo
     host recursion of ``csrc/treeshap.cpp`` runs. ``top_n`` / ``bottom_n`` / ``compare_abs`` follow h2o-py
     (:func:`_sorted_contributions`). ``output_format`` is ``"Original"`` or ``"Compact"``: the two differ in the
     reference only for one-hot encoded XGBoost models, and this engine never one-hot encodes, so they are
-    identical here."""
+    identical here.
+
+    With a ``background_frame`` the contributions are baseline (interventional) SHAP: per row ``x`` and background
+    row ``b`` the Shapley values of ``v(S) = f(x_S, b_~S)``, so the features sum to ``f(x) - f(b)`` and ``BiasTerm``
+    is ``f(b)``; returned as the mean over the background rows, or with ``output_per_reference=True`` as one row
+    per (row, background row) in that order, followed by the int columns ``RowIdx`` and ``BackgroundRowIdx`` (refused
+    with ``ValueError`` past ``H2O_SHAP_MAX_OUT_BYTES``, default 8 GiB). ``output_space=True`` rescales every
+    pair, before averaging, so that it sums to the model's prediction (the probability of a binomial GBM / XGBoost)
+    instead of the margin (``NotImplementedError`` for a custom distribution with a link). A CUDA model runs
+    ``k_shap_baseline`` (``csrc/shap_baseline_kernels.hip``); a CPU model, or ``H2O_SHAP_HIP=0``, the fp64 PyTorch
+    evaluation of the same path table."""
     m = getattr(model, "_model", model)
     if not hasattr(m, "forest") or m.forest is None:
         raise NotImplementedError("predict_contributions is available for tree models (GBM, DRF, XGBoost)")
     if str(output_format).lower() not in ("original", "compact"):
         raise ValueError(f"output_format must be 'Original' or 'Compact', got {output_format!r}")
+    if background_frame is not None:
+        return _baseline_contributions(m, frame, background_frame, bool(output_space), bool(output_per_reference),
+                                       top_n, bottom_n, compare_abs)
+    if output_space or output_per_reference:
+        raise ValueError("output_space and output_per_reference need a background_frame")
     init = getattr(m, "init_f", 0.0)
     init = init[0] if isinstance(init, (list, tuple)) else init
     dev = torch.device(getattr(m, "device", None) or "cpu")

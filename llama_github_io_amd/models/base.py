@@ -276,9 +276,12 @@ class Model:
         return self.output.get("scoring_history")
 
     # ---- explanation (explain.py)
-    def predict_contributions(self, test_data, output_format="Original", top_n=None, bottom_n=None, compare_abs=False):
+    def predict_contributions(self, test_data, output_format="Original", top_n=None, bottom_n=None, compare_abs=False,
+                              background_frame=None, output_space=False, output_per_reference=False):
         from .. import explain
-        return explain.predict_contributions(self, test_data, output_format, top_n, bottom_n, compare_abs)
+        return explain.predict_contributions(self, test_data, output_format, top_n, bottom_n, compare_abs,
+                                             background_frame=background_frame, output_space=output_space,
+                                             output_per_reference=output_per_reference)
 
     def partial_plot(self, data, cols=None, nbins=20, plot=False, targets=None, include_na=False, user_splits=None,
                      **kw):

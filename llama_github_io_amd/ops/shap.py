@@ -22,10 +22,19 @@ path of that element alone. The bias column is ``sum(value * prod(zero_fraction)
 suite's check of the decomposition). A path needs one lane per element, so forests whose longest path has
 more than :data:`MAX_PATH_LEN` (64) elements are not evaluated here: :func:`path_shap` raises for them and
 ``explain.tree_shap_device`` keeps them on the CPU recursion.
+
+:func:`path_shap_baseline` evaluates the same table for baseline (interventional) SHAP: the Shapley values of
+the game ``v(S) = f(x_S, b_~S)`` of a row ``x`` against a background row ``b``. Per path, with the elements
+whose condition holds for ``x`` only (``a`` of them) and for ``b`` only (``c`` of them): nothing if some element
+holds for neither row; else a feature of the first set gets ``+value * T[a][c]``, one of the second
+``-value * T[c][a]``, and the bias cell gets ``value`` when ``a == 0`` (``b`` reaches the leaf), with
+``T[p][q] = (p-1)! q! / (p+q)!``. CUDA tensors run ``k_shap_baseline`` (``csrc/shap_baseline_kernels.hip``), CPU
+tensors a vectorised fp64 PyTorch evaluation with no lane limit.
 """
 from __future__ import annotations
 
 from dataclasses import dataclass, field
+from fractions import Fraction
 
 import numpy as np
 import torch
@@ -37,12 +46,20 @@ c_int, c_ll, c_void_p = nat.c_int, nat.c_ll, nat.c_void_p
 nat.register_hip_signatures({
     # X, N, F, K, G, P, feat, zf, lo, hi, flags, cat_off, cat_nbits, cat_bits, len, value, cls, rounds, out, stream
     "h2o_tree_shap": [c_void_p, c_ll, c_int, c_int, c_int, c_int] + [c_void_p] * 11 + [c_int, c_void_p, c_void_p],
+    # X, N, Bg, B, F, K, G, P, feat, lo, hi, flags, cat_off, cat_nbits, cat_bits, len, value, cls, T, rounds,
+    # per_reference, out, stream
+    "h2o_tree_shap_baseline": [c_void_p, c_ll, c_void_p, c_ll, c_int, c_int, c_int, c_int] + [c_void_p] * 11
+                              + [c_int, c_int, c_void_p, c_void_p],
 })
 
 MAX_PATH_LEN = 64       # one wave lane per path element
 ROW_TILE = 64           # rows per block of k_tree_shap (SHAP_R in csrc/shap_kernels.hip)
 X_TILE_BYTES = 16384    # the block stages X in LDS when F * ROW_TILE * 4 fits (SHAP_X_BYTES)
 PHI_TILE_BYTES = 32768  # ... and accumulates phi in LDS when ROW_TILE * K * (F+1) * 8 fits (SHAP_PHI_BYTES)
+BASELINE_ROW_TILE = 32        # rows per block of k_shap_baseline (SB_R in csrc/shap_baseline_kernels.hip)
+BG_TILE = 32                  # ... and background rows per block (SB_BT)
+BASELINE_X_TILE_BYTES = 12288    # X and background staged in LDS when F * (row tile + BG_TILE) * 4 fits (SB_X_BYTES)
+BASELINE_PHI_TILE_BYTES = 16384  # summed mode: phi in LDS when row tile * K * (F+1) * 8 fits (SB_PHI_BYTES)
 
 NA_OK, IS_CAT, HAS_HI = 1, 2, 4
 
@@ -85,6 +102,23 @@ class PathTable:
                 d[n] = torch.from_numpy(a).to(device)
             self._dev[key] = d
         return self._dev[key]
+
+    def baseline_weights(self, device) -> torch.Tensor:
+        """``T[p][q] = (p-1)! q! / (p+q)!`` as float64 ``[G, G]`` on ``device`` (row 0 is unused and 0): exact
+        rationals rounded once. A path has at most ``G - 1`` real elements, so ``p + q <= G - 1`` is all that is
+        ever read."""
+        d = self.on(device)
+        if "T" not in d:
+            G = max(int(self.G), 1)
+            T = np.zeros((G, G), np.float64)
+            for p in range(1, G):
+                t = Fraction(1, p)
+                for q in range(G):
+                    if q:
+                        t = t * q / (p + q)
+                    T[p, q] = float(t)
+            d["T"] = torch.from_numpy(T).to(device)
+        return d["T"]
 
 
 class _Elem:
@@ -235,14 +269,27 @@ def path_shap(paths: PathTable, X: torch.Tensor, K: int, rounds: int = 0, out: t
     return out
 
 
+def _elements_ok(d: dict, x: torch.Tensor) -> torch.Tensor:
+    """The kernels' condition test: x ``[n, P, G]`` holds, per path element, the row's value of the element's
+    feature -> bool ``[n, P, G]``. NaN and out-of-range categorical codes take ``na_ok``."""
+    flags, cnb, coff, bits = d["flags"], d["cat_nbits"].long(), d["cat_off"].long(), d["cat_bits"].long() & 0xFFFFFFFF
+    na_ok, is_cat, has_hi = (flags & NA_OK) != 0, (flags & IS_CAT) != 0, (flags & HAS_HI) != 0
+    isnan = torch.isnan(x)
+    code = torch.nan_to_num(x, nan=-1.0, posinf=-1.0, neginf=-1.0).clamp(-1.0, 2.0 ** 30).long()
+    inr = (code >= 0) & (code < cnb)
+    cs = torch.where(inr, code, torch.zeros_like(code))
+    word = bits[(coff + (cs >> 5)).clamp(max=bits.numel() - 1)]
+    catok = torch.where(inr, ((word >> (cs & 31)) & 1) != 0, na_ok)
+    numok = (x >= d["lo"]) & (~has_hi | (x < d["hi"]))
+    return torch.where(isnan, na_ok, torch.where(is_cat, catok, numok))
+
+
 def _path_shap_torch(d: dict, G: int, X: torch.Tensor, K: int, out: torch.Tensor) -> None:
     """The kernel's arithmetic, vectorised over (rows, paths, elements): EXTEND builds the permutation
     weights of every path, UNWOUND_SUM removes each element in turn."""
     F, N = X.shape
     P = d["len"].shape[0]
     feat, zf, ln = d["feat"].long(), d["zf"], d["len"].long()
-    flags, cnb, coff, bits = d["flags"], d["cat_nbits"].long(), d["cat_off"].long(), d["cat_bits"].long() & 0xFFFFFFFF
-    na_ok, is_cat, has_hi = (flags & NA_OK) != 0, (flags & IS_CAT) != 0, (flags & HAS_HI) != 0
     e = torch.arange(G)
     real = (e[None, :] >= 1) & (e[None, :] < ln[:, None])           # [P, G]
     fidx = feat.clamp(min=0)
@@ -256,14 +303,7 @@ def _path_shap_torch(d: dict, G: int, X: torch.Tensor, K: int, out: torch.Tensor
     for r0 in range(0, N, step):
         x = X[:, r0:r0 + step].T[:, fidx]                               # [n, P, G]
         n = x.shape[0]
-        isnan = torch.isnan(x)
-        code = torch.nan_to_num(x, nan=-1.0, posinf=-1.0, neginf=-1.0).clamp(-1.0, 2.0 ** 30).long()
-        inr = (code >= 0) & (code < cnb)
-        cs = torch.where(inr, code, torch.zeros_like(code))
-        word = bits[(coff + (cs >> 5)).clamp(max=bits.numel() - 1)]
-        catok = torch.where(inr, ((word >> (cs & 31)) & 1) != 0, na_ok)
-        numok = (x >= d["lo"]) & (~has_hi | (x < d["hi"]))
-        ok = torch.where(isnan, na_ok, torch.where(is_cat, catok, numok))
+        ok = _elements_ok(d, x)
         of = torch.where(real, ok, torch.ones_like(ok)).double()          # dummy and padding: 1
         pw = torch.zeros(n, P, G, dtype=torch.float64)
         pw[:, :, 0] = 1.0
@@ -288,3 +328,90 @@ def _path_shap_torch(d: dict, G: int, X: torch.Tensor, K: int, out: torch.Tensor
             nxt = torch.where(act & hot, pi - tmp * c2 * k.double()[None, :, None], nxt)
         contrib = torch.where(real, tot * (of - zf) * d["value"][None, :, None], torch.zeros_like(tot))
         o2[r0:r0 + n].scatter_add_(1, dst.expand(n, -1), contrib.reshape(n, -1))
+
+
+def path_shap_baseline(paths: PathTable, X: torch.Tensor, B: torch.Tensor, K: int, per_reference: bool = False,
+                       out: torch.Tensor | None = None, rounds: int = 0) -> torch.Tensor:
+    """Baseline SHAP of the rows X against the background rows B, both float32 ``[F, n]`` column-major model
+    matrices on one device -> float64 on that device, margin space, per-tree sums, last column = bias:
+
+    * ``per_reference=False``: ``[N, K, F+1]``, the SUM over the background rows (divide by their number for the mean);
+    * ``per_reference=True``: ``[N * B, K, F+1]``, pair ``(i, j)`` at row ``i * B + j``.
+
+    Per pair the feature cells sum to ``f(x) - f(b)`` and the bias cell is ``f(b)``. ``out``: a contiguous float64
+    tensor of that shape (or with more rows) on X's device to accumulate into instead of a new one. ``rounds`` > 0
+    fixes how many groups of paths one block of the kernel walks. CUDA tensors run ``k_shap_baseline``; CPU
+    tensors, and forests whose longest path has more than :data:`MAX_PATH_LEN` elements, the PyTorch evaluation
+    (for CUDA inputs on the host, the result moved to the device)."""
+    F, N = X.shape
+    if B.dim() != 2 or B.shape[0] != F or B.device != X.device:
+        raise ValueError(f"the background must be a [{F}, n] tensor on {X.device}")
+    nb = int(B.shape[1])
+    if paths.n_features > F:
+        raise ValueError(f"the forest splits on feature {paths.n_features - 1}, X has {F} rows")
+    if int(paths.cls.max(initial=0)) >= K:
+        raise ValueError("a tree's class is outside [0, K)")
+    rows = N * nb if per_reference else N
+    if out is None:
+        out = torch.zeros(rows, K, F + 1, dtype=torch.float64, device=X.device)
+    elif (out.dtype != torch.float64 or out.device != X.device or not out.is_contiguous() or out.dim() != 3
+          or out.shape[0] < rows or tuple(out.shape[1:]) != (K, F + 1)):
+        raise ValueError(f"out must be a contiguous float64 [>= {rows}, {K}, {F + 1}] tensor on {X.device}")
+    if rows == 0 or nb == 0 or not paths.n_paths:
+        return out
+    Xc, Bc = X.contiguous().float(), B.contiguous().float()
+    if X.is_cuda and paths.max_len <= MAX_PATH_LEN:
+        d, T = paths.on(X.device), paths.baseline_weights(X.device)
+        nat.call("h2o_tree_shap_baseline", Xc.data_ptr(), N, Bc.data_ptr(), nb, F, K, paths.G, paths.n_paths,
+                 d["feat"].data_ptr(), d["lo"].data_ptr(), d["hi"].data_ptr(), d["flags"].data_ptr(),
+                 d["cat_off"].data_ptr(), d["cat_nbits"].data_ptr(), d["cat_bits"].data_ptr(), d["len"].data_ptr(),
+                 d["value"].data_ptr(), d["cls"].data_ptr(), T.data_ptr(), int(rounds), int(bool(per_reference)),
+                 out.data_ptr(), nat.stream_ptr(X.device))
+        return out
+    cpu = torch.device("cpu")
+    host = out[:rows] if not X.is_cuda else torch.zeros(rows, K, F + 1, dtype=torch.float64)
+    _path_shap_baseline_torch(paths.on(cpu), paths.G, paths.baseline_weights(cpu), Xc.to(cpu), Bc.to(cpu), K,
+                              bool(per_reference), host)
+    if X.is_cuda:
+        out[:rows] += host.to(X.device)
+    return out
+
+
+def _path_shap_baseline_torch(d: dict, G: int, T: torch.Tensor, X: torch.Tensor, Bg: torch.Tensor, K: int,
+                              per_reference: bool, out: torch.Tensor) -> None:
+    """The kernel's arithmetic, vectorised over (rows, background rows, paths, elements) in chunks of about 4M
+    elements. Element 0 of a path (the dummy root) carries the bias cell, as lane 0 does in the kernel."""
+    F, N = X.shape
+    nb = Bg.shape[1]
+    P = d["len"].shape[0]
+    F1 = F + 1
+    ln = d["len"].long()
+    e = torch.arange(G)
+    real = (e[None, :] >= 1) & (e[None, :] < ln[:, None])             # [P, G]
+    fidx = d["feat"].long().clamp(min=0)
+    cell = torch.where(e[None, :] == 0, torch.full_like(fidx, F), fidx)
+    dst = (d["cls"].long()[:, None] * F1 + cell).reshape(1, -1)
+    val = d["value"][None, None, :, None]
+    cap = max(1, (1 << 22) // max(1, P * G))                         # pairs per chunk
+    m_step = min(nb, cap)
+    n_step = max(1, cap // m_step)
+    o_sum = out.view(-1, K * F1)
+    o_ref = out.view(N, nb, K * F1) if per_reference else None
+    for r0 in range(0, N, n_step):
+        mx = (_elements_ok(d, X[:, r0:r0 + n_step].T[:, fidx]) & real)[:, None]      # [n, 1, P, G]
+        n = mx.shape[0]
+        for c0 in range(0, nb, m_step):
+            mb = (_elements_ok(d, Bg[:, c0:c0 + m_step].T[:, fidx]) & real)[None]    # [1, m, P, G]
+            m = mb.shape[1]
+            xo, bo = mx & ~mb, mb & ~mx
+            alive = ~(real & ~mx & ~mb).any(-1)                        # no element refuses both rows
+            a, c = xo.sum(-1), bo.sum(-1)                               # [n, m, P]
+            w = xo * T[a, c][..., None] - bo * T[c, a][..., None]
+            w[..., 0] = (a == 0).double()                               # b reaches the leaf
+            w = w * alive[..., None] * val
+            if per_reference:
+                t = torch.zeros(n * m, K * F1, dtype=torch.float64)
+                t.scatter_add_(1, dst.expand(n * m, -1), w.reshape(n * m, -1))
+                o_ref[r0:r0 + n, c0:c0 + m] += t.view(n, m, -1)
+            else:
+                o_sum[r0:r0 + n].scatter_add_(1, dst.expand(n, -1), w.sum(1).reshape(n, -1))
