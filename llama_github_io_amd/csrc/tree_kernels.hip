@@ -94,6 +94,9 @@ struct SplitParams {
   // wide-categorical groups (Binning.gcat, null: none): a group's first column = its real columns (1..4), its
   // other columns -1; the first column's block searches one histogram over all of the group's levels
   const int* gcat;
+  // the tree's total weight (written by the root's search), read at depth >= 1: the noise floor of float-weight
+  // histogram entries (see split_find_body); null = none
+  const double* rootw;
 };
 
 // histogram types (SharedTreeParameters.HistogramType) as candidate lattices over the global bins
@@ -1398,6 +1401,16 @@ __device__ __forceinline__ void split_find_body(
     wNA = slot[iNA]; wyNA = slot[iNA + 1]; naYY = slot[iNY]; wYY = slot[iWY];
     if (t < nb && t < NA_BIN) { w = slot[iT]; wy = slot[iT + 1]; }
   }
+  // Float row weights: an entry is the fp64 sum of per-block partials (fixed point times 1 / scale, rounded) and, for
+  // a sibling, parent - built child, so a bin without weight carries rounding residue of either sign that depends on
+  // how the rows fell into blocks (the routed row order is not fixed). Such a bin must read as EMPTY: the occupied
+  // range of the adaptive lattices and ties between thresholds across it otherwise change from run to run. Residue
+  // is ~2^-50 of the root's bin weight; one row of the smallest weight the 2^40 / max fixed point keeps is 2^-40 of
+  // the largest, so entries up to 2^-40 of the tree's total weight are empty. Counts (unit weights, sample masks) are
+  // exact integers: nothing changes for them.
+  const double wtol = (p.rootw != nullptr && level > 0 && p.mode == 0) ? *p.rootw * 0x1p-40 : 0.0;
+  if (wtol > 0 && fabs(w) <= wtol) { w = 0; wy = 0; }
+  if (wtol > 0 && fabs(wNA) <= wtol) { wNA = 0; wyNA = 0; }   // (no NA rows: the NA-left / NA-right candidates tie)
   if (GRP && p.gcat) {
     const int gg = p.gcat[f + f0];
     if (gg < 0) {                       // a group member or padding column: the group's first column searches it
@@ -1519,12 +1532,14 @@ __device__ __forceinline__ void split_find_body(
   if (lt != HT_QUANTILES) {
     __shared__ int a_lo, a_hi, s_guided;
     __shared__ unsigned char smark[256];
-    if (t == 0) { a_lo = 0; a_hi = -1; s_guided = 0; }
+    if (t == 0) { a_lo = 256; a_hi = -1; s_guided = 0; }
     smark[t] = 0;
     __syncthreads();
-    const double cw = sw[t], pw = t > 0 ? sw[t - 1] : 0.0;
-    if (t < nb && cw > 0 && pw == 0) a_lo = t;
-    if (t < nb && W > 0 && cw == W && pw < W) a_hi = t;
+    // first / last bin holding weight, from the bins themselves (numeric column: w is still bin t's own weight).
+    // Not from the prefix sums: with float weights those are inexact and the waves add their predecessors' totals
+    // in different orders, so "sw[t] == W" can hold for no bin at all (no lattice: every threshold searched) or
+    // not, depending on the last bit of the entries. Same bins as before for exact (count) weights.
+    if (t < nb && w > 0) { atomicMin(&a_lo, t); atomicMax(&a_hi, t); }
     __shared__ int r_lo, r_hi;
     const bool ranged = p.range_on != 0;
     if (ranged) {
@@ -1537,7 +1552,7 @@ __device__ __forceinline__ void split_find_body(
       if (up) {
         const double pwt = (t < nb && t < NA_BIN) ? p.hprev[(size_t)rn->parent * slot_doubles + (size_t)t * hs + 2 * f]
                                                   : 0.0;
-        if (pwt > 0) { atomicMin(&r_lo, t); atomicMax(&r_hi, t); }
+        if (pwt > wtol) { atomicMin(&r_lo, t); atomicMax(&r_hi, t); }
       } else if (t < nb && t < NA_BIN && w > 0) {
         atomicMin(&r_lo, t); atomicMax(&r_hi, t);
       }
@@ -3276,7 +3291,7 @@ int h2o_split_find(const void* hist, int slot_doubles, const void* meta, int cap
   p.min_w = min_w; p.min_split_improvement = msi; p.lambda = lambda_; p.alpha = alpha; p.gamma = gamma;
   p.mode = mode; p.random_split = random_split; p.seed = seed; p.hist_type = hist_type; p.fcut = 0;
   p.vrange = nullptr; p.hprev = nullptr; p.pdec = nullptr; p.rnodes = nullptr; p.fgroup = nullptr; p.edges_all = nullptr;
-  p.range_on = 0; p.pad_r = 0; p.gcat = nullptr;
+  p.range_on = 0; p.pad_r = 0; p.gcat = nullptr; p.rootw = nullptr;
   return split_find_launch((void*)hist, slot_doubles, meta, cap, F, nbins_f, iscat_f, mono_f, p, level, cand, root_w,
                            edges, adapt_nb, f0, FL, Derive{nullptr, 0, 0, nullptr, nullptr}, s);
 }
@@ -3602,6 +3617,7 @@ static inline void tp_node_range(const TreePlan* P, int d, const void* hprev, Sp
   p.edges_all = (const float*)P->edges;
   p.pad_r = 0;
   p.gcat = (const int*)P->gcat;
+  p.rootw = d > 0 ? (const double*)P->rootw : nullptr;
 }
 
 // op codes / dtypes of the collective transport

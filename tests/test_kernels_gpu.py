@@ -278,7 +278,7 @@ def test_deeplearning_graph_matches_eager(extra, monkeypatch):
 
 
 @pytest.mark.parametrize("dist", ["gaussian", "bernoulli", "poisson", "gamma", "tweedie", "laplace", "quantile",
-                                  "huber", "quasibinomial"])
+                                  "huber", "quasibinomial", "modified_huber"])
 def test_fused_gbm_step_matches_eager_path(dist, monkeypatch):
     # k_gbm_step (residuals + leaf terms + sampling + f update in one HIP pass) and k_leaf_values
     # == the PyTorch per-distribution path of GBMTrainer on the same device
@@ -287,7 +287,7 @@ def test_fused_gbm_step_matches_eager_path(dist, monkeypatch):
     N, F = 20000, 6
     X = torch.randn(F, N, device=dev, generator=g)
     eta = 0.6 * X[0] - 0.4 * X[1] + 0.3 * X[2] * X[3]
-    if dist in ("bernoulli", "quasibinomial"):
+    if dist in ("bernoulli", "quasibinomial", "modified_huber"):
         y = (torch.rand(N, device=dev, generator=g) < torch.sigmoid(eta)).float()
         dom = ("0", "1")
     elif dist in ("poisson", "tweedie"):
@@ -303,8 +303,6 @@ def test_fused_gbm_step_matches_eager_path(dist, monkeypatch):
     fused = GBMTrainer(dict(params)).fit(X, y, None, None, _info(F, dom))
     monkeypatch.setattr(GBMTrainer, "_fused", lambda self: False)
     eager = GBMTrainer(dict(params)).fit(X, y, None, None, _info(F, dom))
-    a = fused.score_tensor(X).double().cpu()
-    b = eager.score_tensor(X).double().cpu()
     # the row sampling masks come from different generators (hash in-kernel vs torch.rand): compare
     # model quality, and exact structure when sampling is off
     ta, tb = fused.output["training_metrics"], eager.output["training_metrics"]
@@ -317,7 +315,52 @@ def test_fused_gbm_step_matches_eager_path(dist, monkeypatch):
     e1 = GBMTrainer(dict(params)).fit(X, y, None, None, _info(F, dom))
     np.testing.assert_allclose(f1.score_tensor(X).double().cpu().numpy(), e1.score_tensor(X).double().cpu().numpy(),
                                rtol=2e-4, atol=2e-5)
-    _ = (a, b)
+
+
+@pytest.mark.parametrize("dist", ["bernoulli", "poisson"])
+def test_fused_gbm_step_weights_offset_matches_eager_path(dist, monkeypatch):
+    # the fused step with a user weights vector (w != nullptr, zeros included) and an offset in f. Non-integer
+    # weights also make the histogram entries inexact fp64 sums: the split search must not let their last bits
+    # decide which bins are occupied (k_split_find), or two fits of the same data grow different trees
+    from llama_github_io_amd.models.gbm import GBMTrainer
+    g = torch.Generator(device=dev).manual_seed(6)
+    N, F = 20000, 6
+    X = torch.randn(F, N, device=dev, generator=g)
+    eta = 0.6 * X[0] - 0.4 * X[1] + 0.3 * X[2] * X[3]
+    w = 3 * torch.rand(N, device=dev, generator=g)
+    w[::13] = 0
+    offset = 0.3 * torch.randn(N, device=dev, generator=g)
+    if dist == "bernoulli":
+        y = (torch.rand(N, device=dev, generator=g) < torch.sigmoid(eta + offset)).float()
+        dom = ("0", "1")
+    else:
+        y = torch.poisson(torch.exp(eta + offset), generator=g)
+        dom = None
+    params = dict(ntrees=8, max_depth=4, seed=3, distribution=dist, sample_rate=1.0)
+    tr = GBMTrainer(dict(params))
+    f1 = tr.fit(X, y, w, offset, _info(F, dom))
+    assert tr._fused() and tr._wbuf is not None
+    monkeypatch.setattr(GBMTrainer, "_fused", lambda self: False)
+    e1 = GBMTrainer(dict(params)).fit(X, y, w, offset, _info(F, dom))
+    np.testing.assert_allclose(f1.score_tensor(X, offset).double().cpu().numpy(),
+                               e1.score_tensor(X, offset).double().cpu().numpy(), rtol=2e-4, atol=2e-5)
+
+
+@pytest.mark.parametrize("hist", ["AUTO", "QuantilesGlobal"])
+def test_gbm_float_weights_grow_the_same_trees_twice(hist, monkeypatch):
+    # non-integer row weights: the routed row order (and with it the last bits of the fp64 histogram entries) changes
+    # from fit to fit; the trees must not. Depth 6: the adaptive lattice is coarser than the bins from level 3 on.
+    from llama_github_io_amd.models.gbm import GBMTrainer
+    g = torch.Generator(device=dev).manual_seed(6)
+    N, F = 20000, 6
+    X = torch.randn(F, N, device=dev, generator=g)
+    w = 3 * torch.rand(N, device=dev, generator=g)
+    w[::13] = 0
+    y = 0.6 * X[0] - 0.4 * X[1] + 0.3 * X[2] * X[3] + 0.3 * torch.randn(N, device=dev, generator=g)
+    params = dict(ntrees=4, max_depth=6, seed=3, distribution="gaussian", sample_rate=1.0, histogram_type=hist)
+    fits = [GBMTrainer(dict(params)).fit(X, y, w, None, _info(F, None)) for _ in range(3)]
+    trees = [[(t.feat.tolist(), t.thr.tolist()) for t in m.forest.trees] for m in fits]
+    assert trees[1] == trees[0] and trees[2] == trees[0]
 
 
 @pytest.mark.parametrize("N,P,R", [(1000, 7, 1), (70001, 51, 1), (5000, 130, 3), (33, 200, 8), (37, 13001, 2)])
