@@ -9,10 +9,14 @@ scoreContributions`` (predict_contributions), ``hex/PartialDependence.java`` (pa
   sorted ``top_n`` / ``bottom_n`` pairs of h2o-py. With a ``background_frame``: baseline (interventional) SHAP
   against its rows (``csrc/shap_baseline_kernels.hip`` on a CUDA model), averaged or per reference, in the margin
   or the output space.
-* ``partial_plot``: for each grid value of a column (equally spaced over [min, max] / levels) the
-  column is overwritten on device and the whole frame re-scored (one forest-kernel launch per grid
-  point): mean, sd, std err; 2-D pairs, multinomial targets, ICE rows, weights.
-* ``h``: Friedman–Popescu H² from centred partial dependences on the training rows.
+* ``partial_plot``: mean, sd, std err of the response with a column (or a column pair) set to each grid value
+  (equally spaced over [min, max] / levels); multinomial targets, ICE rows, weights. A tree model on a CUDA
+  device (GBM, DRF, XGBoost tree boosters, isolation forest) gets the margins of every (grid tuple, row) from one
+  pass of the grid-forking kernel (``Forest.predict_raw_grid`` / ``csrc/pdp_kernels.hip``: no copy of the model
+  matrix, one tree walk per distinct leaf) and the response from ``Model.score_from_raw``; ``H2O_PDP_HIP=0``,
+  CPU models and every other model overwrite the column and re-score the frame once per grid value.
+* ``h``: Friedman–Popescu H² from centred partial dependences on the training rows (same two paths; the grid
+  tuples are the sampled rows' own values).
 * ``feature_interaction``: xgbfi statistics of split-feature paths (gain, F-score, weighted F-score,
   expected gain, ranks), leaf statistics and split-value histograms.
 """
@@ -267,11 +271,82 @@ def _pdp_grid(col, nbins, user_splits, include_na):
     return vals, labels
 
 
+def _pd_stats(r, w):
+    """(mean, sd, se) of the responses ``r`` [n] float64, weighted by ``w`` [n] float64 when given."""
+    if w is None:
+        mu = float(r.mean())
+        sd = float(r.std()) if r.numel() > 1 else 0.0
+        return mu, sd, sd / math.sqrt(max(r.numel(), 1))
+    ws = float(w.sum())
+    mu = float((w * r).sum() / ws)
+    sd = math.sqrt(float((w * (r - mu) ** 2).sum()) / max(ws - 1.0, 1e-300))
+    return mu, sd, sd / math.sqrt(max(ws, 1e-300))
+
+
+PDP_CHUNK_BYTES = 256 << 20     # margins [G, n, K] fp32 of one row chunk of the device path
+
+
+def _pdp_on_device(m, X) -> bool:
+    """The grid kernel path: a CUDA model matrix, a model that scores from forest margins, no ``H2O_PDP_HIP=0``."""
+    ok = getattr(m, "scores_from_raw", None)
+    return bool(X.is_cuda and os.environ.get("H2O_PDP_HIP", "1") != "0" and ok is not None and ok())
+
+
+def _grid_response(m, X, off, js, V, pick):
+    """Response ``[G, n]`` float64 of the rows of X under every grid tuple (``V[s][g]`` replaces feature
+    ``js[s]``): ``Forest.predict_raw_grid`` margins, ``Model.score_from_raw``; the offset broadcasts over tuples."""
+    raw = m.forest.predict_raw_grid(X, js, V)
+    G, n, K = raw.shape
+    P = m.score_from_raw(raw.view(G * n, K), None if off is None else off.repeat(G))
+    return pick(P).double().view(G, n)
+
+
+def _grid_stats(m, X, off, w, js, V, pick):
+    """(mean, sd, se) per grid tuple. Rows go in chunks whose margins stay under :data:`PDP_CHUNK_BYTES`; one chunk
+    uses :func:`_pd_stats` (the expressions of the re-scoring path) per tuple, several are merged as (weight, mean, M2) in
+    fp64 with Chan's update."""
+    G, N = int(V.shape[1]), int(X.shape[1])
+    step = max(1, PDP_CHUNK_BYTES // max(1, G * m.forest.K * 4))
+    if step >= N:
+        r = _grid_response(m, X, off, js, V, pick)
+        return [_pd_stats(r[g], w) for g in range(G)]
+    W = np.zeros(G)
+    mu = np.zeros(G)
+    M2 = np.zeros(G)
+    for r0 in range(0, N, step):
+        r = _grid_response(m, X[:, r0:r0 + step], None if off is None else off[r0:r0 + step], js, V, pick)
+        if w is None:
+            wb = torch.full((G,), float(r.shape[1]), dtype=torch.float64, device=r.device)
+            mb = r.mean(1)
+            sb = ((r - mb[:, None]) ** 2).sum(1)
+        else:
+            wc = w[r0:r0 + step]
+            wb = wc.sum().expand(G)
+            mb = (wc * r).sum(1) / wb
+            sb = (wc * (r - mb[:, None]) ** 2).sum(1)
+        wb, mb, sb = (t.cpu().numpy() for t in (wb, mb, sb))
+        tot = W + wb
+        d = mb - mu
+        f = np.divide(wb, tot, out=np.zeros(G), where=tot != 0)
+        mu = mu + d * f
+        M2 = M2 + sb + d * d * W * f
+        W = tot
+    out = []
+    for g in range(G):
+        if w is None:
+            sd = math.sqrt(M2[g] / (N - 1)) if N > 1 else 0.0
+            out.append((float(mu[g]), sd, sd / math.sqrt(max(N, 1))))
+        else:
+            sd = math.sqrt(M2[g] / max(W[g] - 1.0, 1e-300))
+            out.append((float(mu[g]), sd, sd / math.sqrt(max(W[g], 1e-300))))
+    return out
+
+
 def partial_plot(model, frame, cols=None, nbins=20, targets=None, include_na=False, user_splits=None,
                  weight_column=None, row_index=-1, col_pairs_2dpdp=None):
     """Partial dependence (reference ``hex/PartialDependence.java``): for each grid value the column
-    (or column pair) is overwritten on device for every row and the frame re-scored; mean, weighted
-    standard deviation and standard error of the response. ``targets`` picks classes of a multinomial
+    (or column pair) is set to it for every row and the frame scored; mean, weighted standard deviation and
+    standard error of the response (device path and ``H2O_PDP_HIP``: module docstring). ``targets`` picks classes of a multinomial
     model (one table per column and class), ``row_index`` >= 0 gives an ICE curve of that row.
     Returns ``{name: [row dicts]}`` with name = column, ``"a|b"`` for pairs, ``"col|class"`` with targets."""
     m = getattr(model, "_model", model)
@@ -294,21 +369,16 @@ def partial_plot(model, frame, cols=None, nbins=20, targets=None, include_na=Fal
         tidx = [(None, 1 if m.model_category == "Binomial" else 0)]
     user_splits = user_splits or {}
 
-    def response(Xg, k):
-        P = m.score_tensor(Xg, off)
+    def pick(P, k):
         if P.dim() == 1:
             return P.double()
         return P[:, k].double() if m.model_category in ("Binomial", "Multinomial") else P[:, 0].double()
 
+    def response(Xg, k):
+        return pick(m.score_tensor(Xg, off), k)
+
     def stats(r):
-        if w is None:
-            mu = float(r.mean())
-            sd = float(r.std()) if r.numel() > 1 else 0.0
-            return mu, sd, sd / math.sqrt(max(r.numel(), 1))
-        ws = float(w.sum())
-        mu = float((w * r).sum() / ws)
-        sd = math.sqrt(float((w * (r - mu) ** 2).sum()) / max(ws - 1.0, 1e-300))
-        return mu, sd, sd / math.sqrt(max(ws, 1e-300))
+        return _pd_stats(r, w)
 
     out = {}
     jobs = [(c,) for c in cols] + [tuple(pr) for pr in (col_pairs_2dpdp or [])]
@@ -321,11 +391,19 @@ def partial_plot(model, frame, cols=None, nbins=20, targets=None, include_na=Fal
                 combos = [((v,), (lab,)) for v, lab in zip(*grids[0])]
             else:
                 combos = [((v1, v2), (l1, l2)) for v1, l1 in zip(*grids[0]) for v2, l2 in zip(*grids[1])]
-            for vals, labs in combos:
-                Xg = X.clone()
-                for j, v in zip(js, vals):
-                    Xg[j] = float(v)
-                mu, sd, se = stats(response(Xg, k))
+            on_device = _pdp_on_device(m, X) and len(set(js)) == len(js)
+            if on_device:
+                V = torch.tensor([[float(v[s]) for v, _ in combos] for s in range(len(js))], dtype=torch.float32,
+                                 device=X.device).view(len(js), len(combos))
+                done = _grid_stats(m, X, off, w, js, V, lambda P: pick(P, k))
+            for ci, (vals, labs) in enumerate(combos):
+                if on_device:
+                    mu, sd, se = done[ci]
+                else:
+                    Xg = X.clone()
+                    for j, v in zip(js, vals):
+                        Xg[j] = float(v)
+                    mu, sd, se = stats(response(Xg, k))
                 row = dict(value=labs[0], mean_response=mu, stddev_response=sd, std_error_mean_response=se)
                 if len(cc) == 2:
                     row["value2"] = labs[1]
@@ -338,6 +416,11 @@ def partial_plot(model, frame, cols=None, nbins=20, targets=None, include_na=Fal
 def _pd_rows(m, X, off, cols, jidx):
     """Partial dependence of the columns ``cols`` evaluated AT each training row's own values."""
     N = X.shape[1]
+    if N and _pdp_on_device(m, X) and len(set(jidx)) == len(jidx):
+        # the tuples are the rows' own values of the columns; one mean per tuple, reduced as the loop below does
+        r = _grid_response(m, X, off, jidx, X[jidx], lambda P: P[:, -1] if P.dim() == 2 else P)
+        res = torch.stack([r[i].mean() for i in range(N)])
+        return res - res.mean()
     res = torch.zeros(N, dtype=torch.float64, device=X.device)
     vals = X[jidx].T  # [N, len]
     for i in range(N):

@@ -185,6 +185,22 @@ class Model:
             P = correct_probabilities(P, self.output["prior_class_distrib"], bal)
         return P
 
+    def scores_from_raw(self) -> bool:
+        """True for a tree model whose prediction is a function of ``Forest.predict_raw``'s margins alone
+        (:meth:`score_from_raw`): GBM, DRF, the tree boosters of XGBoost, isolation forest."""
+        return (hasattr(self, "_response_from_raw") and getattr(self, "forest", None) is not None
+                and self.output.get("booster") != "gblinear")
+
+    def score_from_raw(self, raw: torch.Tensor, offset=None) -> torch.Tensor:
+        """:meth:`score_tensor` of the rows whose forest margins are ``raw`` [N, K] (``Forest.predict_raw``):
+        the same post-processing, ``balance_classes`` correction included, without walking the forest again."""
+        P = self._response_from_raw(raw.to(self.device), None if offset is None else offset.to(self.device))
+        bal = self.output.get("model_class_distrib") if isinstance(self.output, dict) else None
+        if bal and P.dim() == 2 and P.shape[1] == len(bal):
+            from .adapt import correct_probabilities
+            P = correct_probabilities(P, self.output["prior_class_distrib"], bal)
+        return P
+
     def _adapt(self, frame):
         """Replay the model's preprocessors (AutoML target encoding: ``Model.Parameters._preprocessors``),
         then the training frame's categorical encoding / interaction columns (models/adapt.py)."""

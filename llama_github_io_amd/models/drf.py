@@ -32,7 +32,10 @@ class DRFModel(SharedTreeModel):
         return self.output.get("trees_per_iter", 1)
 
     def _predict_tensor(self, X, offset=None):
-        s = self.forest.predict_raw(X)
+        return self._response_from_raw(self.forest.predict_raw(X), offset)
+
+    def _response_from_raw(self, s, offset=None):
+        """The prediction from the forest's leaf sums ``s`` [N, K] (``Forest.predict_raw``)."""
         n = max(1, self.ntrees_built())
         cat = self.model_category
         if cat == "Regression":

@@ -56,7 +56,10 @@ class GBMModel(SharedTreeModel):
         return self.forest.K if self.forest is not None else 1
 
     def _predict_tensor(self, X, offset=None):
-        f = self.forest.predict_raw(X)
+        return self._response_from_raw(self.forest.predict_raw(X), offset)
+
+    def _response_from_raw(self, f, offset=None):
+        """The prediction from the forest's margins ``f`` [N, K] (``Forest.predict_raw``)."""
         init = torch.as_tensor(self.init_f, dtype=torch.float32, device=f.device)
         f = f + init
         if offset is not None:

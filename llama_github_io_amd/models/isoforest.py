@@ -42,7 +42,11 @@ class IsolationForestModel(SharedTreeModel):
     algo = "isolationforest"
 
     def _predict_tensor(self, X, offset=None):
-        s = self.forest.predict_raw(X)[:, 0].double()
+        return self._response_from_raw(self.forest.predict_raw(X), offset)
+
+    def _response_from_raw(self, raw, offset=None):
+        """The prediction from the forest's path-length sums ``raw`` [N, 1] (``Forest.predict_raw``)."""
+        s = raw[:, 0].double()
         n = max(1, len(self.forest))
         mn, mx = self.output["min_path_length"], self.output["max_path_length"]
         score = (mx - s) / (mx - mn) if mx > mn else torch.ones_like(s)

@@ -73,9 +73,14 @@ class XGBoostModel(SharedTreeModel):
     def _predict_tensor(self, X, offset=None):
         if self.output.get("booster") == "gblinear":
             Z = self.expander.transform(X)
-            f = Z @ self.beta.to(Z.device).T + self.bias.to(Z.device)
-        else:
-            f = self.forest.predict_raw(X) + torch.as_tensor(self.init_f, dtype=torch.float32, device=X.device)
+            return self._link(Z @ self.beta.to(Z.device).T + self.bias.to(Z.device), offset)
+        return self._response_from_raw(self.forest.predict_raw(X), offset)
+
+    def _response_from_raw(self, raw, offset=None):
+        """The prediction of a tree booster from the forest's margins ``raw`` [N, K] (``Forest.predict_raw``)."""
+        return self._link(raw + torch.as_tensor(self.init_f, dtype=torch.float32, device=raw.device), offset)
+
+    def _link(self, f, offset):
         if offset is not None:
             f = f + offset.float()[:, None]
         d = self.output["distribution"]

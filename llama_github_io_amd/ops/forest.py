@@ -6,6 +6,8 @@ A :class:`Tree` is a flat node table (root = 0): ``feat`` (-1 = leaf), raw-value
 ``cover`` (weighted rows, used by TreeSHAP) and split ``gain`` (variable importance).
 :class:`Forest` concatenates trees (with their class index) and scores raw features either with the
 HIP kernel ``k_predict`` (CUDA tensors) or a vectorised PyTorch traversal (CPU).
+:meth:`Forest.predict_raw_grid` scores the rows once per grid tuple of a feature set (partial dependence,
+``explain.py``): ``k_predict_grid`` of ``csrc/pdp_kernels.hip`` on CUDA tensors, overwrite-and-rescore on CPU.
 """
 from __future__ import annotations
 
@@ -16,6 +18,16 @@ import torch
 
 from . import _native as nat
 from .tree import NA_BIN, TreeLevels
+
+nat.register_hip_signatures({
+    # X, N, K, feat, thr, left, right, na_left, cat_off, cat_bits, cat_nbits, value, roots, cls, n_trees, n_nodes,
+    # sel, V, G, masks, featx, ws_chunks, out, stream
+    "h2o_predict_grid": [nat.c_void_p, nat.c_ll, nat.c_int] + [nat.c_void_p] * 11 + [nat.c_int, nat.c_int]
+                        + [nat.c_void_p] * 2 + [nat.c_ll] + [nat.c_void_p] * 2 + [nat.c_int] + [nat.c_void_p] * 2,
+})
+
+PD_CHUNK = 64               # grid tuples per chunk of k_predict_grid (PD_CHUNK in csrc/pdp_kernels.hip)
+PD_MASK_BYTES = 64 << 20    # node masks of the chunks of one launch: 8 bytes per (chunk, node)
 
 
 @dataclass
@@ -253,6 +265,61 @@ class Forest:
         else:
             self._predict_torch(Xc, fl, nt, out, leaves)
         return (out, leaves) if return_leaves else out
+
+    def predict_raw_grid(self, X: torch.Tensor, feats, V, t0: int = 0, t1: int | None = None,
+                         out: torch.Tensor | None = None) -> torch.Tensor:
+        """:meth:`predict_raw` of X once per grid tuple: tuple ``g`` replaces row ``feats[s]`` of X by ``V[s][g]``
+        for every ``s``. X: float32 [F, N]; ``feats``: distinct feature indices (a feature no tree splits on, or
+        every feature, is fine); V: float32 [len(feats), G]. Returns [G, N, K] float32 on X's device, cell
+        ``(g, i, c)`` bit-equal to ``predict_raw`` of the overwritten matrix. CUDA tensors run the forking walk of
+        ``csrc/pdp_kernels.hip`` (no copy of X, one walk per distinct leaf); CPU tensors overwrite and re-score.
+        ``out``: a contiguous float32 tensor on X's device with at least ``G * N * K`` elements; the result is then
+        a view of its first ``G * N * K`` (every one of them is written, nothing after them)."""
+        t1 = len(self.trees) if t1 is None else t1
+        F, N = X.shape
+        feats = [int(f) for f in feats]
+        V = torch.as_tensor(V, dtype=torch.float32, device=X.device).reshape(len(feats), -1)
+        G = int(V.shape[1])
+        if len(set(feats)) != len(feats) or any(f < 0 or f >= F for f in feats):
+            raise ValueError(f"feats must be distinct indices in [0, {F}), got {feats}")
+        if out is None:
+            out = torch.empty(G, N, self.K, dtype=torch.float32, device=X.device)
+        elif (out.dtype != torch.float32 or out.device != X.device or not out.is_contiguous()
+              or out.numel() < G * N * self.K):
+            raise ValueError(f"out must be a contiguous float32 tensor of >= {G * N * self.K} elements on {X.device}")
+        else:
+            out = out.view(-1)[:G * N * self.K].view(G, N, self.K)
+        nt = t1 - t0
+        if nt <= 0 or N == 0 or G == 0:
+            return out.zero_()
+        if not X.is_cuda:
+            Xg = X.float().clone()
+            for g in range(G):
+                for s, f in enumerate(feats):
+                    Xg[f] = V[s, g]
+                out[g] = self.predict_raw(Xg, t0, t1)
+            return out
+        fl = self._device_flat(X.device, t0, t1)
+        key = (str(X.device), t0, t1, "nfeat")
+        if key not in self._flat:
+            self._flat[key] = int(fl["feat"].max()) + 1
+        if self._flat[key] > F:
+            raise ValueError(f"the forest splits on feature {self._flat[key] - 1}, X has {F} rows")
+        n_nodes = int(fl["feat"].numel())
+        Xc, Vc = X.contiguous().float(), V.contiguous()
+        sel = torch.full((F,), -1, dtype=torch.int32)
+        sel[feats] = torch.arange(len(feats), dtype=torch.int32)
+        sel = sel.to(X.device)
+        n_chunks = (G + PD_CHUNK - 1) // PD_CHUNK
+        ws_chunks = max(1, min(n_chunks, PD_MASK_BYTES // (8 * n_nodes)))
+        masks = torch.empty(ws_chunks * n_nodes, dtype=torch.int64, device=X.device)
+        featx = torch.empty(n_nodes, dtype=torch.int32, device=X.device)
+        nat.call("h2o_predict_grid", Xc.data_ptr(), N, self.K, fl["feat"].data_ptr(), fl["thr"].data_ptr(),
+                 fl["left"].data_ptr(), fl["right"].data_ptr(), fl["na_left"].data_ptr(), fl["cat_off"].data_ptr(),
+                 fl["cat_bits"].data_ptr(), fl["cat_nbits"].data_ptr(), fl["value"].data_ptr(),
+                 fl["roots"].data_ptr(), fl["cls"].data_ptr(), nt, n_nodes, sel.data_ptr(), Vc.data_ptr(), G,
+                 masks.data_ptr(), featx.data_ptr(), ws_chunks, out.data_ptr(), nat.stream_ptr(X.device))
+        return out
 
     @staticmethod
     def _predict_torch(X, fl, nt, out, leaves):
