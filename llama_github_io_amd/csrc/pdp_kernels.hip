@@ -1,14 +1,15 @@
 // Partial dependence on device (gfx950): score every row of X through the forest once per GRID TUPLE, where a
 // tuple g replaces the row's values of a feature set S by V[s][g]. out[G][N][K] (fp32): cell (g, i, c) is the sum,
 // over the trees of class c in forest order, of the leaf that row i reaches under tuple g: bit for bit what
-// k_predict (tree_kernels.hip) gives on a copy of X whose S rows were overwritten with tuple g.
+// k_predict (predict_kernels.hip) gives on a copy of X whose S rows were overwritten with tuple g: both walks decide
+// every split with forest_go_left (forest_view.h) and add the leaves in the same order.
 //
 // Down one row's path only the splits on a feature of S depend on the tuple, so most tuples share their leaf. The
 // walk forks on the tuples instead of repeating itself per tuple:
 //
 // k_pd_node_masks: one thread per (node, chunk of at most 64 tuples). For a split on a feature of S it writes a
-//   64-bit mask, bit g = "tuple g of the chunk goes left", from k_predict's own expression (NaN and categorical
-//   codes outside [0, cat_nbits) take na_left, else the bitset bit; numeric x < thr in fp32). Chunk 0 also writes
+//   64-bit mask, bit g = "tuple g of the chunk goes left", from forest_go_left (NaN and categorical codes
+//   outside [0, cat_nbits) take na_left, else the bitset bit; numeric x < thr in fp32). Chunk 0 also writes
 //   featx[node]: the node's feature with PD_SEL set when it is in S (-1 for a leaf), which is what the walk reads
 //   instead of feat.
 // k_predict_grid: one lane owns one row, a block is ONE wave (64 rows) and one chunk of tuples and one class
@@ -30,6 +31,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "forest_view.h"
+
 namespace {
 
 constexpr int PD_CHUNK = 64;            // tuples per chunk: one bit each of a node mask (PD_CHUNK in ops/forest.py)
@@ -37,13 +40,11 @@ constexpr int PD_ROWS = 64;             // rows per block: one wave
 constexpr int PD_SEL = 1 << 30;         // featx bit: the split's feature is in S
 
 __global__ __launch_bounds__(256) void k_pd_node_masks(
-    int n_nodes, const int* __restrict__ feat, const float* __restrict__ thr, const int* __restrict__ na_left,
-    const int* __restrict__ cat_off, const unsigned* __restrict__ cat_bits, const int* __restrict__ cat_nbits,
-    const int* __restrict__ sel, const float* __restrict__ V, long long G, long long g_begin,
+    ForestView fv, const int* __restrict__ sel, const float* __restrict__ V, long long G, long long g_begin,
     unsigned long long* __restrict__ masks /*[chunks of this launch][n_nodes]*/, int* __restrict__ featx) {
   const int n = blockIdx.x * blockDim.x + threadIdx.x;
-  if (n >= n_nodes) return;
-  const int f = feat[n];
+  if (n >= fv.n_nodes) return;
+  const int f = fv.feat[n];
   const int s = f >= 0 ? sel[f] : -1;
   if (blockIdx.y == 0) featx[n] = f < 0 ? -1 : (s >= 0 ? (f | PD_SEL) : f);
   unsigned long long m = 0ull;
@@ -52,27 +53,16 @@ __global__ __launch_bounds__(256) void k_pd_node_masks(
     const int gc = (int)((G - g0) < (long long)PD_CHUNK ? (G - g0) : (long long)PD_CHUNK);
     const float* v = V + (long long)s * G + g0;
     for (int g = 0; g < gc; ++g) {
-      const float x = v[g];
-      bool go_left;
-      if (x != x) go_left = na_left[n] != 0;
-      else if (cat_off[n] >= 0) {
-        const int code = (int)x;
-        if (code < 0 || code >= cat_nbits[n]) go_left = na_left[n] != 0;
-        else go_left = (cat_bits[cat_off[n] + (code >> 5)] >> (code & 31)) & 1u;
-      } else go_left = x < thr[n];
-      if (go_left) m |= 1ull << g;
+      if (forest_go_left(fv, n, v[g])) m |= 1ull << g;
     }
   }
-  masks[(long long)blockIdx.y * n_nodes + n] = m;
+  masks[(long long)blockIdx.y * fv.n_nodes + n] = m;
 }
 
 __global__ __launch_bounds__(PD_ROWS) void k_predict_grid(
-    const float* __restrict__ X, long long N, int K, long long G, long long g_begin, int n_nodes,
-    const int* __restrict__ featx, const float* __restrict__ thr, const int* __restrict__ left,
-    const int* __restrict__ right, const int* __restrict__ na_left, const int* __restrict__ cat_off,
-    const unsigned* __restrict__ cat_bits, const int* __restrict__ cat_nbits, const float* __restrict__ value,
-    const int* __restrict__ tree_root, const int* __restrict__ tree_cls, int n_trees,
-    const unsigned long long* __restrict__ masks, float* __restrict__ out /*[G][N][K]*/) {
+    const float* __restrict__ X, long long N, int K, long long G, long long g_begin, ForestView fv,
+    const int* __restrict__ featx, const unsigned long long* __restrict__ masks,
+    float* __restrict__ out /*[G][N][K]*/) {
   extern __shared__ float acc[];          // [tuples of the launch's largest chunk][PD_ROWS]
   const int lane = threadIdx.x;
   const long long row = (long long)blockIdx.x * PD_ROWS + lane;
@@ -81,13 +71,13 @@ __global__ __launch_bounds__(PD_ROWS) void k_predict_grid(
   const int cls = blockIdx.z;
   if (row >= N || gc <= 0) return;       // no barrier in this kernel: a lane may leave
   const unsigned long long full = gc >= 64 ? ~0ull : ((1ull << gc) - 1ull);
-  const unsigned long long* nm = masks + (long long)blockIdx.y * n_nodes;
+  const unsigned long long* nm = masks + (long long)blockIdx.y * fv.n_nodes;
   float* a = acc + lane;
   for (int g = 0; g < gc; ++g) a[g * PD_ROWS] = 0.0f;
 
-  for (int t = 0; t < n_trees; ++t) {
-    if (tree_cls[t] != cls) continue;
-    const int root = tree_root[t];
+  for (int t = 0; t < fv.n_trees; ++t) {
+    if (fv.cls[t] != cls) continue;
+    const int root = fv.roots[t];
     unsigned long long rem = full;
     while (rem) {
       const int first = __ffsll((unsigned long long)rem) - 1;
@@ -101,18 +91,12 @@ __global__ __launch_bounds__(PD_ROWS) void k_predict_grid(
           go_left = (k >> first) & 1ull;
           m &= go_left ? k : ~k;
         } else {
-          const float x = X[(long long)fx * N + row];
-          if (x != x) go_left = na_left[n] != 0;
-          else if (cat_off[n] >= 0) {
-            const int code = (int)x;
-            if (code < 0 || code >= cat_nbits[n]) go_left = na_left[n] != 0;
-            else go_left = (cat_bits[cat_off[n] + (code >> 5)] >> (code & 31)) & 1u;
-          } else go_left = x < thr[n];
+          go_left = forest_go_left(fv, n, X[(long long)fx * N + row]);
         }
-        n = go_left ? left[n] : right[n];
+        n = go_left ? fv.left[n] : fv.right[n];
         fx = featx[n];
       }
-      const float v = value[n];
+      const float v = fv.value[n];
       rem &= ~m;
       while (m) {
         const int g = __ffsll((unsigned long long)m) - 1;
@@ -128,33 +112,25 @@ __global__ __launch_bounds__(PD_ROWS) void k_predict_grid(
 
 extern "C" {
 
-// X: float32 [F][N]; the flat forest arrays of Forest.flatten (n_nodes nodes, n_trees trees); sel: int32 [F], -1 or
-// the position of the feature in S; V: float32 [|S|][G]. out: float32 [G][N][K], every cell is written. Workspace:
-// masks uint64 [ws_chunks][n_nodes], featx int32 [n_nodes]. Tuples go in launches of at most ws_chunks chunks of 64.
-int h2o_predict_grid(const void* X, long long N, int K, const void* feat, const void* thr, const void* left,
-                     const void* right, const void* na_left, const void* cat_off, const void* cat_bits,
-                     const void* cat_nbits, const void* value, const void* tree_root, const void* tree_cls,
-                     int n_trees, int n_nodes, const void* sel, const void* V, long long G, void* masks,
-                     void* featx, int ws_chunks, void* out, void* stream) {
-  if (N <= 0 || G <= 0 || n_trees <= 0 || n_nodes <= 0) return 0;
+// X: float32 [F][N]; fv: the flat forest (host pointer, read here); sel: int32 [F], -1 or the position of the
+// feature in S; V: float32 [|S|][G]. out: float32 [G][N][K], every cell is written. Workspace: masks uint64
+// [ws_chunks][n_nodes], featx int32 [n_nodes]. Tuples go in launches of at most ws_chunks chunks of 64.
+int h2o_predict_grid(const void* X, long long N, int K, const ForestView* fv, const void* sel, const void* V,
+                     long long G, void* masks, void* featx, int ws_chunks, void* out, hipStream_t s) {
+  if (N <= 0 || G <= 0 || fv->n_trees <= 0 || fv->n_nodes <= 0) return 0;
   const long long tiles = (N + PD_ROWS - 1) / PD_ROWS;
   if (K <= 0 || K > 65535 || ws_chunks <= 0 || tiles > 0x7fffffffLL) return (int)hipErrorInvalidValue;
-  hipStream_t s = (hipStream_t)stream;
   if (ws_chunks > 65535) ws_chunks = 65535;      // grid y
   const long long per_launch = (long long)ws_chunks * PD_CHUNK;
   for (long long g_begin = 0; g_begin < G; g_begin += per_launch) {
     const long long left_g = G - g_begin;
     const unsigned chunks = (unsigned)(((left_g < per_launch ? left_g : per_launch) + PD_CHUNK - 1) / PD_CHUNK);
     const size_t lds = (size_t)(left_g < PD_CHUNK ? left_g : PD_CHUNK) * PD_ROWS * sizeof(float);
-    hipLaunchKernelGGL(k_pd_node_masks, dim3((unsigned)((n_nodes + 255) / 256), chunks), dim3(256), 0, s, n_nodes,
-                       (const int*)feat, (const float*)thr, (const int*)na_left, (const int*)cat_off,
-                       (const unsigned*)cat_bits, (const int*)cat_nbits, (const int*)sel, (const float*)V, G, g_begin,
-                       (unsigned long long*)masks, (int*)featx);
+    hipLaunchKernelGGL(k_pd_node_masks, dim3((unsigned)((fv->n_nodes + 255) / 256), chunks), dim3(256), 0, s, *fv,
+                       (const int*)sel, (const float*)V, G, g_begin, (unsigned long long*)masks, (int*)featx);
     hipLaunchKernelGGL(k_predict_grid, dim3((unsigned)tiles, chunks, (unsigned)K), dim3(PD_ROWS), lds, s,
-                       (const float*)X, N, K, G, g_begin, n_nodes, (const int*)featx, (const float*)thr,
-                       (const int*)left, (const int*)right, (const int*)na_left, (const int*)cat_off,
-                       (const unsigned*)cat_bits, (const int*)cat_nbits, (const float*)value, (const int*)tree_root,
-                       (const int*)tree_cls, n_trees, (const unsigned long long*)masks, (float*)out);
+                       (const float*)X, N, K, G, g_begin, *fv, (const int*)featx,
+                       (const unsigned long long*)masks, (float*)out);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
   }

@@ -1,6 +1,7 @@
 // Path-decomposed TreeSHAP on device (gfx950). Formulation: Mitchell, Frank, Holmes, "GPUTreeShap:
 // massively parallel exact calculation of SHAP scores for tree ensembles" (2020); the path table is built by
-// ops/shap.py (forest_paths), the recursion this replaces on device is csrc/treeshap.cpp.
+// ops/shap.py (forest_paths), the recursion this replaces on device is csrc/treeshap.cpp. What this kernel shares
+// with k_shap_baseline (the table's device view, element load, condition test, phi tile) is path_table.h's.
 //
 // k_tree_shap<G>: lanes are path elements. A path is padded to G lanes (G = 8/16/32/64, the smallest that
 // holds the forest's longest path), 64/G paths share a wave, a block of 256 threads holds 256/G paths per
@@ -18,10 +19,12 @@
 // launches of about SHAP_PAIRS (row, path) pairs each.
 //
 // Resource usage (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage):
-//   G = 8: 64 VGPR    G = 16: 62 VGPR    G = 32: 62 VGPR    G = 64: 58 VGPR
+//   G = 8: 62 VGPR    G = 16: 62 VGPR    G = 32: 60 VGPR    G = 64: 56 VGPR
 //   every instantiation: 0 bytes of scratch, 0 VGPR / SGPR spills, occupancy 8 waves per SIMD
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "path_table.h"
 
 namespace {
 
@@ -32,16 +35,11 @@ constexpr int SHAP_RCP = 72;            // 1/k for k = 1..65, padded
 constexpr int SHAP_X_BYTES = 16384;
 constexpr int SHAP_PHI_BYTES = 32768;
 constexpr long long SHAP_PAIRS = 1LL << 34;  // (row, path) pairs per launch
-constexpr int SHAP_NA_OK = 1, SHAP_IS_CAT = 2, SHAP_HAS_HI = 4;
 
 template <int G>
 __global__ __launch_bounds__(SHAP_THREADS) void k_tree_shap(
-    const float* __restrict__ X, long long N, long long row_begin, long long row_end, int F, int K, int P,
-    const int* __restrict__ e_feat,
-    const double* __restrict__ e_zf, const float* __restrict__ e_lo, const float* __restrict__ e_hi,
-    const int* __restrict__ e_flags, const int* __restrict__ e_coff, const int* __restrict__ e_cnb,
-    const uint32_t* __restrict__ cat_bits, const int* __restrict__ p_len, const double* __restrict__ p_val,
-    const int* __restrict__ p_cls, int rounds, int use_x, int use_phi, double* __restrict__ out) {
+    const float* __restrict__ X, long long N, long long row_begin, long long row_end, int F, int K, PathView pv,
+    int rounds, int use_x, int use_phi, double* __restrict__ out) {
   extern __shared__ double smem[];
   double* s_rcp = smem;
   double* s_zf = smem + SHAP_RCP;
@@ -58,7 +56,7 @@ __global__ __launch_bounds__(SHAP_THREADS) void k_tree_shap(
   const int nrows = (int)((row_end - row0) < (long long)SHAP_R ? (row_end - row0) : (long long)SHAP_R);
 
   if (tid < SHAP_RCP) s_rcp[tid] = tid ? 1.0 / (double)tid : 0.0;
-  for (int i = tid; i < phi_n; i += SHAP_THREADS) s_phi[i] = 0.0;
+  phi_tile_zero<SHAP_THREADS>(s_phi, phi_n);
   if (use_x) {
     for (int i = tid; i < F * SHAP_R; i += SHAP_THREADS) {
       const int f = i / SHAP_R, r = i - f * SHAP_R;
@@ -68,49 +66,32 @@ __global__ __launch_bounds__(SHAP_THREADS) void k_tree_shap(
 
   for (int round = 0; round < rounds; ++round) {
     const long long first = ((long long)blockIdx.y * rounds + round) * (SHAP_THREADS / G);
-    if (first >= P) break;
+    if (first >= pv.P) break;
     const int p = (int)first + tid / G;
-    const bool valid = p < P;
-    int feat = -1, flags = SHAP_NA_OK, coff = 0, cnb = 0, len = 1, cls = 0;
-    double zf = 1.0, val = 0.0;
-    float lo = 0.0f, hi = 0.0f;
-    if (valid) {
-      const long long q = (long long)p * G + e;
-      feat = e_feat[q]; zf = e_zf[q]; lo = e_lo[q]; hi = e_hi[q];
-      flags = e_flags[q]; coff = e_coff[q]; cnb = e_cnb[q];
-      len = p_len[p]; val = p_val[p]; cls = p_cls[p];
-    }
+    const bool valid = p < pv.P;
+    double zf = 1.0;
+    const PathElem el = path_elem_load<G>(pv, p, e, &zf);
     __syncthreads();                    // the X / phi staging above, and last round's readers of s_zf
     s_zf[tid] = zf;
     __syncthreads();
 
-    int ml = len;                       // longest path of this wave: the wave-uniform trip count
+    int ml = el.len;                       // longest path of this wave: the wave-uniform trip count
 #pragma unroll
     for (int o = 32; o >= G; o >>= 1) ml = max(ml, __shfl_xor(ml, o));
     ml = __builtin_amdgcn_readfirstlane(ml);
 
-    const bool real = e >= 1 && e < len;
-    const int fx = feat < 0 ? 0 : feat;
-    const bool na_ok = flags & SHAP_NA_OK, is_cat = flags & SHAP_IS_CAT, has_hi = flags & SHAP_HAS_HI;
-    const int d = len - 1;              // index of the path's last element
+    const bool real = e >= 1 && e < el.len;
+    const int fx = el.feat < 0 ? 0 : el.feat;
+    const int d = el.len - 1;              // index of the path's last element
     const double c1 = (double)(d + 1);
     const double c2 = zf * s_rcp[d + 1];
     const double c3 = c1 / zf;
     const double* gzf = s_zf + (tid & ~(G - 1));
-    const long long o_base = ((long long)cls * F1 + fx);
+    const long long o_base = ((long long)el.cls * F1 + fx);
 
     for (int r = 0; r < nrows; ++r) {
       const float v = use_x ? s_x[fx * SHAP_RS + r] : X[(long long)fx * N + row0 + r];
-      bool ok;
-      if (v != v) {
-        ok = na_ok;
-      } else if (is_cat) {
-        const int code = (int)v;
-        ok = (code >= 0 && code < cnb) ? ((cat_bits[coff + (code >> 5)] >> (code & 31)) & 1u) != 0 : na_ok;
-      } else {
-        ok = v >= lo && (!has_hi || v < hi);
-      }
-      const bool hot = ok || !real;     // dummy root and padding: one_fraction 1
+      const bool hot = path_elem_ok(el, pv.cat_bits, v) || !real;     // dummy root and padding: one_fraction 1
       const unsigned long long ofm = __ballot(hot) >> gb;
 
       // EXTEND: pweight of the path built from elements 0..dd
@@ -122,7 +103,7 @@ __global__ __launch_bounds__(SHAP_THREADS) void k_tree_shap(
         const double a = gzf[dd] * ((double)(dd - e) * rd);
         const double b = ((ofm >> dd) & 1ull) ? (double)e * rd : 0.0;
         const double nw = pw * a + left * b;
-        pw = dd < len ? nw : pw;
+        pw = dd < el.len ? nw : pw;
       }
 
       // UNWOUND_SUM for this lane's element
@@ -141,74 +122,51 @@ __global__ __launch_bounds__(SHAP_THREADS) void k_tree_shap(
         }
       }
       if (real && valid) {
-        const double c = total * ((hot ? 1.0 : 0.0) - zf) * val;
+        const double c = total * ((hot ? 1.0 : 0.0) - zf) * el.val;
         if (use_phi) atomicAdd(&s_phi[(long long)r * K * F1 + o_base], c);
         else unsafeAtomicAdd(&out[(row0 + r) * K * F1 + o_base], c);
       }
     }
   }
 
-  if (use_phi) {
-    __syncthreads();
-    double* o = out + row0 * K * F1;
-    const int n = nrows * K * F1;
-    for (int i = tid; i < n; i += SHAP_THREADS) {
-      const double c = s_phi[i];
-      if (c != 0.0) unsafeAtomicAdd(&o[i], c);
-    }
-  }
+  if (use_phi) phi_tile_flush<SHAP_THREADS>(s_phi, out + row0 * K * F1, nrows * K * F1);
 }
 
 }  // namespace
 
 extern "C" {
 
-// X: float32 [F][N]; element arrays [P][G], path arrays [P] (ops/shap.py PathTable); out: float64
-// [N][K][F+1], accumulated into (the caller zeroes it; the bias column is the caller's). rounds: groups of
-// 256/G paths per block, 0 = pick from the grid size.
-int h2o_tree_shap(const void* X, long long N, int F, int K, int G, int P, const void* e_feat, const void* e_zf,
-                  const void* e_lo, const void* e_hi, const void* e_flags, const void* e_coff, const void* e_cnb,
-                  const void* cat_bits, const void* p_len, const void* p_val, const void* p_cls, int rounds,
-                  void* out, void* stream) {
-  if (N <= 0 || P <= 0) return 0;
-  if (F <= 0 || K <= 0 || (G != 8 && G != 16 && G != 32 && G != 64)) return (int)hipErrorInvalidValue;
-  hipStream_t s = (hipStream_t)stream;
-  const long long per_round = SHAP_THREADS / G;
-  const long long total_rounds = (P + per_round - 1) / per_round;
+// the compiled tile constants: the tests size their cases from the mirrors in ops/shap.py
+int h2o_shap_tiles(int* out) {
+  out[0] = SHAP_R; out[1] = SHAP_X_BYTES; out[2] = SHAP_PHI_BYTES;
+  return 0;
+}
+
+// X: float32 [F][N]; pv: the path table (host pointer, read here); out: float64 [N][K][F+1], accumulated into (the
+// caller zeroes it; the bias column is the caller's). rounds: groups of 256/G paths per block, 0 = pick from the
+// grid size.
+int h2o_tree_shap(const void* X, long long N, int F, int K, const PathView* pv, int rounds, void* out,
+                  hipStream_t s) {
+  if (N <= 0 || pv->P <= 0) return 0;
+  if (F <= 0 || K <= 0 || !path_G_ok(pv->G)) return (int)hipErrorInvalidValue;
   // rows of one launch: whole tiles, about SHAP_PAIRS (row, path) pairs, so no launch runs for long
-  long long rows_per_launch = (SHAP_PAIRS / P) / SHAP_R * SHAP_R;
+  long long rows_per_launch = (SHAP_PAIRS / pv->P) / SHAP_R * SHAP_R;
   if (rows_per_launch < SHAP_R) rows_per_launch = SHAP_R;
   if (rows_per_launch > N) rows_per_launch = N;
-  const long long row_tiles = (rows_per_launch + SHAP_R - 1) / SHAP_R;
-  if (rounds <= 0) {
-    // about 2048 blocks when there is that much work; small N spreads over the chip through the paths
-    long long r = total_rounds * row_tiles / 2048;
-    rounds = (int)(r < 1 ? 1 : r > 32 ? 32 : r);
-  }
-  const long long min_rounds = (total_rounds + 65534) / 65535;
-  if (rounds < min_rounds) rounds = (int)min_rounds;
-  const long long chunks = (total_rounds + rounds - 1) / rounds;
+  const unsigned chunks = path_plan_rounds(*pv, SHAP_THREADS, (rows_per_launch + SHAP_R - 1) / SHAP_R, &rounds);
   const int use_x = (long long)F * SHAP_R * 4 <= SHAP_X_BYTES;
   const int use_phi = (long long)SHAP_R * K * (F + 1) * 8 <= SHAP_PHI_BYTES;
   size_t lds = (size_t)(SHAP_RCP + SHAP_THREADS) * 8;
   if (use_phi) lds += (size_t)SHAP_R * K * (F + 1) * 8;
   if (use_x) lds += (size_t)F * SHAP_RS * 4;
-  const dim3 block(SHAP_THREADS);
-#define SHAP_LAUNCH(GG)                                                                                            \
-  hipLaunchKernelGGL((k_tree_shap<GG>), grid, block, lds, s, (const float*)X, N, r0, r1, F, K, P,                  \
-                     (const int*)e_feat,                                                                           \
-                     (const double*)e_zf, (const float*)e_lo, (const float*)e_hi, (const int*)e_flags,             \
-                     (const int*)e_coff, (const int*)e_cnb, (const uint32_t*)cat_bits, (const int*)p_len,          \
-                     (const double*)p_val, (const int*)p_cls, rounds, use_x, use_phi, (double*)out)
   for (long long r0 = 0; r0 < N; r0 += rows_per_launch) {
     const long long r1 = r0 + rows_per_launch < N ? r0 + rows_per_launch : N;
-    const dim3 grid((unsigned)((r1 - r0 + SHAP_R - 1) / SHAP_R), (unsigned)chunks);
-    if (G == 8) SHAP_LAUNCH(8);
-    else if (G == 16) SHAP_LAUNCH(16);
-    else if (G == 32) SHAP_LAUNCH(32);
-    else SHAP_LAUNCH(64);
+    const dim3 grid((unsigned)((r1 - r0 + SHAP_R - 1) / SHAP_R), chunks);
+    path_dispatch(pv->G, false, [&](auto g, auto) {
+      hipLaunchKernelGGL((k_tree_shap<decltype(g)::value>), grid, dim3(SHAP_THREADS), lds, s, (const float*)X, N, r0,
+                         r1, F, K, *pv, rounds, use_x, use_phi, (double*)out);
+    });
   }
-#undef SHAP_LAUNCH
   return (int)hipGetLastError();
 }
 

@@ -2805,39 +2805,6 @@ __global__ __launch_bounds__(256) void k_bin_assign(const float* __restrict__ X,
 }
 
 // ------------------------------------------------------------------------------------------------
-// k_predict: score raw features through a compressed forest.
-//   X: column-major fp32 [F][N]. Forest nodes (SoA): feat (-1 leaf), thr, left, right (absolute node
-//   index), na_left, cat_off (-1 numeric; else word offset into cat_bits), value. tree_root[t], tree_cls[t].
-//   out[N][K] += value of each tree's leaf (class tree_cls[t]).
-__global__ void k_predict(const float* __restrict__ X, long long N, int K,
-                          const int* __restrict__ feat, const float* __restrict__ thr,
-                          const int* __restrict__ left, const int* __restrict__ right,
-                          const int* __restrict__ na_left, const int* __restrict__ cat_off,
-                          const unsigned* __restrict__ cat_bits, const int* __restrict__ cat_nbits,
-                          const float* __restrict__ value, const int* __restrict__ tree_root,
-                          const int* __restrict__ tree_cls, int n_trees, float* __restrict__ out,
-                          int* __restrict__ leaf_out /*nullable [N][n_trees]*/) {
-  const long long row = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (row >= N) return;
-  for (int t = 0; t < n_trees; ++t) {
-    int n = tree_root[t];
-    while (feat[n] >= 0) {
-      const float x = X[(long long)feat[n] * N + row];
-      bool go_left;
-      if (x != x) go_left = na_left[n] != 0;
-      else if (cat_off[n] >= 0) {
-        const int code = (int)x;
-        if (code < 0 || code >= cat_nbits[n]) go_left = na_left[n] != 0;
-        else go_left = (cat_bits[cat_off[n] + (code >> 5)] >> (code & 31)) & 1u;
-      } else go_left = x < thr[n];
-      n = go_left ? left[n] : right[n];
-    }
-    out[row * K + tree_cls[t]] += value[n];
-    if (leaf_out) leaf_out[row * n_trees + t] = n;
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
 // Fixed-point scales: max |w|, |wY| (int64 LDS histograms) and max |num|, |den| (int64 leaf sums) of the SoA
 // aux planes aux[c * N + i] -> AMAX_SHARDS x 4 shard maxima (uint bits of non-negative floats)
 __global__ __launch_bounds__(256) void k_amax(const float* __restrict__ aux, long long N, unsigned* __restrict__ amax_bits) {
@@ -3524,20 +3491,6 @@ int h2o_bin_assign(const void* X, long long N, int F, int stride, const void* ed
                      (const int*)xmap);
   return (int)hipGetLastError();
 }
-
-int h2o_predict(const void* X, long long N, int K, const void* feat, const void* thr, const void* left,
-                const void* right, const void* na_left, const void* cat_off, const void* cat_bits,
-                const void* cat_nbits, const void* value, const void* tree_root, const void* tree_cls, int n_trees,
-                void* out, void* leaf_out, hipStream_t s) {
-  const int blk = 256;
-  const long long grid = (N + blk - 1) / blk;
-  hipLaunchKernelGGL(k_predict, dim3((unsigned)grid), dim3(blk), 0, s, (const float*)X, N, K, (const int*)feat,
-                     (const float*)thr, (const int*)left, (const int*)right, (const int*)na_left,
-                     (const int*)cat_off, (const unsigned*)cat_bits, (const int*)cat_nbits, (const float*)value,
-                     (const int*)tree_root, (const int*)tree_cls, n_trees, (float*)out, (int*)leaf_out);
-  return (int)hipGetLastError();
-}
-
 
 // ================================================================================================
 // Native per-tree launch sequence: a tree costs a handful of host calls instead of ~45 ctypes round trips

@@ -71,14 +71,13 @@ _HIP_SIGS = {
     "h2o_gbm_step": [c_ll, c_ll, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_float, c_ull,
                      ctypes.c_float, c_void_p, c_void_p, c_int, c_void_p],
     "h2o_add_leaf": [c_ll, c_void_p, c_int, c_void_p, c_void_p, c_void_p],
-    "h2o_predict": [c_void_p, c_ll, c_int] + [c_void_p] * 11 + [c_int, c_void_p, c_void_p, c_void_p],
 }
 
 
 # Bumped whenever a C launcher's argument list changes; every native library exports h2o_abi_version()
 # (csrc/abi.h) and a library built from older sources is refused instead of being called with shifted
 # arguments.
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 
 def _check_abi(lib, name: str) -> None:

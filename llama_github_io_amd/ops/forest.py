@@ -5,12 +5,13 @@ A :class:`Tree` is a flat node table (root = 0): ``feat`` (-1 = leaf), raw-value
 (numeric: ``x < thr`` goes left), ``na_left``, categorical level bitsets, children, leaf ``value``,
 ``cover`` (weighted rows, used by TreeSHAP) and split ``gain`` (variable importance).
 :class:`Forest` concatenates trees (with their class index) and scores raw features either with the
-HIP kernel ``k_predict`` (CUDA tensors) or a vectorised PyTorch traversal (CPU).
+HIP kernel ``k_predict`` of ``csrc/predict_kernels.hip`` (CUDA tensors) or a vectorised PyTorch traversal (CPU).
 :meth:`Forest.predict_raw_grid` scores the rows once per grid tuple of a feature set (partial dependence,
 ``explain.py``): ``k_predict_grid`` of ``csrc/pdp_kernels.hip`` on CUDA tensors, overwrite-and-rescore on CPU.
 """
 from __future__ import annotations
 
+import ctypes
 from dataclasses import dataclass
 
 import numpy as np
@@ -19,11 +20,21 @@ import torch
 from . import _native as nat
 from .tree import NA_BIN, TreeLevels
 
+FLAT_ARRAYS = ("feat", "thr", "left", "right", "na_left", "cat_off", "cat_bits", "cat_nbits", "value", "roots", "cls")
+
+
+class ForestView(ctypes.Structure):
+    """``ForestView`` of ``csrc/forest_view.h``: the device pointers of :meth:`Forest.flatten`'s arrays."""
+    _fields_ = [(n, nat.c_void_p) for n in FLAT_ARRAYS] + [("n_trees", nat.c_int), ("n_nodes", nat.c_int)]
+
+
+_view_p = ctypes.POINTER(ForestView)
 nat.register_hip_signatures({
-    # X, N, K, feat, thr, left, right, na_left, cat_off, cat_bits, cat_nbits, value, roots, cls, n_trees, n_nodes,
-    # sel, V, G, masks, featx, ws_chunks, out, stream
-    "h2o_predict_grid": [nat.c_void_p, nat.c_ll, nat.c_int] + [nat.c_void_p] * 11 + [nat.c_int, nat.c_int]
-                        + [nat.c_void_p] * 2 + [nat.c_ll] + [nat.c_void_p] * 2 + [nat.c_int] + [nat.c_void_p] * 2,
+    # X, N, K, forest, out, leaf_out, stream
+    "h2o_predict": [nat.c_void_p, nat.c_ll, nat.c_int, _view_p] + [nat.c_void_p] * 3,
+    # X, N, K, forest, sel, V, G, masks, featx, ws_chunks, out, stream
+    "h2o_predict_grid": [nat.c_void_p, nat.c_ll, nat.c_int, _view_p] + [nat.c_void_p] * 2 + [nat.c_ll]
+                        + [nat.c_void_p] * 2 + [nat.c_int] + [nat.c_void_p] * 2,
 })
 
 PD_CHUNK = 64               # grid tuples per chunk of k_predict_grid (PD_CHUNK in csrc/pdp_kernels.hip)
@@ -240,7 +251,11 @@ class Forest:
         key = (str(device), t0, t1)
         if key not in self._flat:
             fl = self.flatten(t0, t1)
-            self._flat[key] = {k: torch.from_numpy(np.ascontiguousarray(v)).to(device) for k, v in fl.items()}
+            d = {k: torch.from_numpy(np.ascontiguousarray(v)).to(device) for k, v in fl.items()}
+            # the launchers' view of these tensors: cached with them, so one dict keeps both alive
+            d["n_features"] = int(fl["feat"].max(initial=-1)) + 1
+            d["view"] = ForestView(*(d[k].data_ptr() for k in FLAT_ARRAYS), n_trees=t1 - t0, n_nodes=d["feat"].numel())
+            self._flat[key] = d
         return self._flat[key]
 
     def predict_raw(self, X: torch.Tensor, t0: int = 0, t1: int | None = None, out: torch.Tensor | None = None,
@@ -257,11 +272,8 @@ class Forest:
         fl = self._device_flat(X.device, t0, t1)
         Xc = X.contiguous().float()
         if X.is_cuda:
-            nat.call("h2o_predict", Xc.data_ptr(), N, self.K, fl["feat"].data_ptr(), fl["thr"].data_ptr(),
-                     fl["left"].data_ptr(), fl["right"].data_ptr(), fl["na_left"].data_ptr(), fl["cat_off"].data_ptr(),
-                     fl["cat_bits"].data_ptr(), fl["cat_nbits"].data_ptr(), fl["value"].data_ptr(),
-                     fl["roots"].data_ptr(), fl["cls"].data_ptr(), nt, out.data_ptr(),
-                     0 if leaves is None else leaves.data_ptr(), nat.stream_ptr(X.device))
+            nat.call("h2o_predict", Xc.data_ptr(), N, self.K, fl["view"], out.data_ptr(), nat.ptr(leaves),
+                     nat.stream_ptr(X.device))
         else:
             self._predict_torch(Xc, fl, nt, out, leaves)
         return (out, leaves) if return_leaves else out
@@ -300,11 +312,8 @@ class Forest:
                 out[g] = self.predict_raw(Xg, t0, t1)
             return out
         fl = self._device_flat(X.device, t0, t1)
-        key = (str(X.device), t0, t1, "nfeat")
-        if key not in self._flat:
-            self._flat[key] = int(fl["feat"].max()) + 1
-        if self._flat[key] > F:
-            raise ValueError(f"the forest splits on feature {self._flat[key] - 1}, X has {F} rows")
+        if fl["n_features"] > F:
+            raise ValueError(f"the forest splits on feature {fl['n_features'] - 1}, X has {F} rows")
         n_nodes = int(fl["feat"].numel())
         Xc, Vc = X.contiguous().float(), V.contiguous()
         sel = torch.full((F,), -1, dtype=torch.int32)
@@ -314,10 +323,7 @@ class Forest:
         ws_chunks = max(1, min(n_chunks, PD_MASK_BYTES // (8 * n_nodes)))
         masks = torch.empty(ws_chunks * n_nodes, dtype=torch.int64, device=X.device)
         featx = torch.empty(n_nodes, dtype=torch.int32, device=X.device)
-        nat.call("h2o_predict_grid", Xc.data_ptr(), N, self.K, fl["feat"].data_ptr(), fl["thr"].data_ptr(),
-                 fl["left"].data_ptr(), fl["right"].data_ptr(), fl["na_left"].data_ptr(), fl["cat_off"].data_ptr(),
-                 fl["cat_bits"].data_ptr(), fl["cat_nbits"].data_ptr(), fl["value"].data_ptr(),
-                 fl["roots"].data_ptr(), fl["cls"].data_ptr(), nt, n_nodes, sel.data_ptr(), Vc.data_ptr(), G,
+        nat.call("h2o_predict_grid", Xc.data_ptr(), N, self.K, fl["view"], sel.data_ptr(), Vc.data_ptr(), G,
                  masks.data_ptr(), featx.data_ptr(), ws_chunks, out.data_ptr(), nat.stream_ptr(X.device))
         return out
 

@@ -33,6 +33,7 @@ tensors a vectorised fp64 PyTorch evaluation with no lane limit.
 """
 from __future__ import annotations
 
+import ctypes
 from dataclasses import dataclass, field
 from fractions import Fraction
 
@@ -43,13 +44,23 @@ from . import _native as nat
 
 c_int, c_ll, c_void_p = nat.c_int, nat.c_ll, nat.c_void_p
 
+PATH_ARRAYS = ("feat", "zf", "lo", "hi", "flags", "cat_off", "cat_nbits", "cat_bits", "len", "value", "cls")
+
+
+class PathView(ctypes.Structure):
+    """``PathView`` of ``csrc/path_table.h``: the device pointers of a :class:`PathTable`'s arrays."""
+    _fields_ = [(n, c_void_p) for n in PATH_ARRAYS] + [("P", c_int), ("G", c_int)]
+
+
+_view_p = ctypes.POINTER(PathView)
 nat.register_hip_signatures({
-    # X, N, F, K, G, P, feat, zf, lo, hi, flags, cat_off, cat_nbits, cat_bits, len, value, cls, rounds, out, stream
-    "h2o_tree_shap": [c_void_p, c_ll, c_int, c_int, c_int, c_int] + [c_void_p] * 11 + [c_int, c_void_p, c_void_p],
-    # X, N, Bg, B, F, K, G, P, feat, lo, hi, flags, cat_off, cat_nbits, cat_bits, len, value, cls, T, rounds,
-    # per_reference, out, stream
-    "h2o_tree_shap_baseline": [c_void_p, c_ll, c_void_p, c_ll, c_int, c_int, c_int, c_int] + [c_void_p] * 11
-                              + [c_int, c_int, c_void_p, c_void_p],
+    # X, N, F, K, paths, rounds, out, stream
+    "h2o_tree_shap": [c_void_p, c_ll, c_int, c_int, _view_p, c_int, c_void_p, c_void_p],
+    # X, N, Bg, B, F, K, paths, T, rounds, per_reference, out, stream
+    "h2o_tree_shap_baseline": [c_void_p, c_ll, c_void_p, c_ll, c_int, c_int, _view_p, c_void_p, c_int, c_int, c_void_p,
+                               c_void_p],
+    "h2o_shap_tiles": [c_void_p],               # int32 [3]: ROW_TILE, X_TILE_BYTES, PHI_TILE_BYTES as compiled
+    "h2o_shap_baseline_tiles": [c_void_p],      # int32 [4]: BASELINE_ROW_TILE, BG_TILE, BASELINE_X / PHI_TILE_BYTES
 })
 
 MAX_PATH_LEN = 64       # one wave lane per path element
@@ -93,13 +104,14 @@ class PathTable:
     def on(self, device) -> dict:
         key = str(device)
         if key not in self._dev:
-            names = ("feat", "zf", "lo", "hi", "flags", "cat_off", "cat_nbits", "cat_bits", "len", "value", "cls", "bias")
             d = {}
-            for n in names:
+            for n in PATH_ARRAYS + ("bias",):
                 a = np.ascontiguousarray(getattr(self, n))
                 if a.dtype == np.uint32:
                     a = a.view(np.int32)
                 d[n] = torch.from_numpy(a).to(device)
+            # the launchers' view of these tensors: cached with them, so one dict keeps both alive
+            d["view"] = PathView(*(d[n].data_ptr() for n in PATH_ARRAYS), P=self.n_paths, G=self.G)
             self._dev[key] = d
         return self._dev[key]
 
@@ -236,6 +248,21 @@ def forest_paths(forest) -> PathTable:
     return t
 
 
+def _check_shap_args(paths: PathTable, X: torch.Tensor, K: int, rows: int, out: torch.Tensor | None) -> torch.Tensor:
+    """The checks of :func:`path_shap` and :func:`path_shap_baseline`; returns ``out``, or a new zeroed one if None."""
+    F = X.shape[0]
+    if paths.n_features > F:
+        raise ValueError(f"the forest splits on feature {paths.n_features - 1}, X has {F} rows")
+    if int(paths.cls.max(initial=0)) >= K:
+        raise ValueError("a tree's class is outside [0, K)")
+    if out is None:
+        return torch.zeros(rows, K, F + 1, dtype=torch.float64, device=X.device)
+    if (out.dtype != torch.float64 or out.device != X.device or not out.is_contiguous() or out.dim() != 3
+            or out.shape[0] < rows or tuple(out.shape[1:]) != (K, F + 1)):
+        raise ValueError(f"out must be a contiguous float64 [>= {rows}, {K}, {F + 1}] tensor on {X.device}")
+    return out
+
+
 def path_shap(paths: PathTable, X: torch.Tensor, K: int, rounds: int = 0, out: torch.Tensor | None = None) -> torch.Tensor:
     """X: float32 ``[F, N]`` column-major model matrix -> contributions ``[N, K, F+1]`` float64 on X's
     device (margin space, per-tree sums, last column = bias). ``rounds`` > 0 fixes how many groups of
@@ -244,25 +271,15 @@ def path_shap(paths: PathTable, X: torch.Tensor, K: int, rounds: int = 0, out: t
     if paths.max_len > MAX_PATH_LEN:
         raise ValueError(f"longest path has {paths.max_len} elements, more than the {MAX_PATH_LEN} lanes of a wave")
     F, N = X.shape
-    if paths.n_features > F:
-        raise ValueError(f"the forest splits on feature {paths.n_features - 1}, X has {F} rows")
-    if int(paths.cls.max(initial=0)) >= K:
-        raise ValueError("a tree's class is outside [0, K)")
-    if out is None:
-        out = torch.zeros(N, K, F + 1, dtype=torch.float64, device=X.device)
-    elif (out.dtype != torch.float64 or out.device != X.device or not out.is_contiguous() or out.dim() != 3
-          or out.shape[0] < N or tuple(out.shape[1:]) != (K, F + 1)):
-        raise ValueError(f"out must be a contiguous float64 [>= {N}, {K}, {F + 1}] tensor on {X.device}")
+    out = _check_shap_args(paths, X, K, N, out)
     if N == 0:
         return out
     Xc = X.contiguous().float()
     d = paths.on(X.device)
     if paths.n_paths:
         if X.is_cuda:
-            nat.call("h2o_tree_shap", Xc.data_ptr(), N, F, K, paths.G, paths.n_paths, d["feat"].data_ptr(),
-                     d["zf"].data_ptr(), d["lo"].data_ptr(), d["hi"].data_ptr(), d["flags"].data_ptr(),
-                     d["cat_off"].data_ptr(), d["cat_nbits"].data_ptr(), d["cat_bits"].data_ptr(), d["len"].data_ptr(),
-                     d["value"].data_ptr(), d["cls"].data_ptr(), int(rounds), out.data_ptr(), nat.stream_ptr(X.device))
+            nat.call("h2o_tree_shap", Xc.data_ptr(), N, F, K, d["view"], int(rounds), out.data_ptr(),
+                     nat.stream_ptr(X.device))
         else:
             _path_shap_torch(d, paths.G, Xc, K, out[:N])
     out[:N, :paths.bias.shape[0], F] += d["bias"][:K]
@@ -347,26 +364,15 @@ def path_shap_baseline(paths: PathTable, X: torch.Tensor, B: torch.Tensor, K: in
     if B.dim() != 2 or B.shape[0] != F or B.device != X.device:
         raise ValueError(f"the background must be a [{F}, n] tensor on {X.device}")
     nb = int(B.shape[1])
-    if paths.n_features > F:
-        raise ValueError(f"the forest splits on feature {paths.n_features - 1}, X has {F} rows")
-    if int(paths.cls.max(initial=0)) >= K:
-        raise ValueError("a tree's class is outside [0, K)")
     rows = N * nb if per_reference else N
-    if out is None:
-        out = torch.zeros(rows, K, F + 1, dtype=torch.float64, device=X.device)
-    elif (out.dtype != torch.float64 or out.device != X.device or not out.is_contiguous() or out.dim() != 3
-          or out.shape[0] < rows or tuple(out.shape[1:]) != (K, F + 1)):
-        raise ValueError(f"out must be a contiguous float64 [>= {rows}, {K}, {F + 1}] tensor on {X.device}")
+    out = _check_shap_args(paths, X, K, rows, out)
     if rows == 0 or nb == 0 or not paths.n_paths:
         return out
     Xc, Bc = X.contiguous().float(), B.contiguous().float()
     if X.is_cuda and paths.max_len <= MAX_PATH_LEN:
         d, T = paths.on(X.device), paths.baseline_weights(X.device)
-        nat.call("h2o_tree_shap_baseline", Xc.data_ptr(), N, Bc.data_ptr(), nb, F, K, paths.G, paths.n_paths,
-                 d["feat"].data_ptr(), d["lo"].data_ptr(), d["hi"].data_ptr(), d["flags"].data_ptr(),
-                 d["cat_off"].data_ptr(), d["cat_nbits"].data_ptr(), d["cat_bits"].data_ptr(), d["len"].data_ptr(),
-                 d["value"].data_ptr(), d["cls"].data_ptr(), T.data_ptr(), int(rounds), int(bool(per_reference)),
-                 out.data_ptr(), nat.stream_ptr(X.device))
+        nat.call("h2o_tree_shap_baseline", Xc.data_ptr(), N, Bc.data_ptr(), nb, F, K, d["view"], T.data_ptr(),
+                 int(rounds), int(bool(per_reference)), out.data_ptr(), nat.stream_ptr(X.device))
         return out
     cpu = torch.device("cpu")
     host = out[:rows] if not X.is_cuda else torch.zeros(rows, K, F + 1, dtype=torch.float64)

@@ -64,10 +64,7 @@ def kernel_ms(paths, X, K):
     out = torch.zeros(N, K, Fx + 1, dtype=torch.float64, device=X.device)
 
     def launch():
-        nat.call("h2o_tree_shap", X.data_ptr(), N, Fx, K, paths.G, paths.n_paths, d["feat"].data_ptr(), d["zf"].data_ptr(),
-                 d["lo"].data_ptr(), d["hi"].data_ptr(), d["flags"].data_ptr(), d["cat_off"].data_ptr(),
-                 d["cat_nbits"].data_ptr(), d["cat_bits"].data_ptr(), d["len"].data_ptr(), d["value"].data_ptr(),
-                 d["cls"].data_ptr(), 0, out.data_ptr(), nat.stream_ptr(X.device))
+        nat.call("h2o_tree_shap", X.data_ptr(), N, Fx, K, d["view"], 0, out.data_ptr(), nat.stream_ptr(X.device))
 
     if N <= 100_000:
         launch()

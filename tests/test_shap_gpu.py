@@ -13,7 +13,7 @@ import torch
 import h2o
 from h2o.estimators import H2OGradientBoostingEstimator, H2ORandomForestEstimator, H2OXGBoostEstimator
 from llama_github_io_amd import explain
-from llama_github_io_amd.ops import shap
+from llama_github_io_amd.ops import _native as nat, shap
 
 import shap_cases as sc
 
@@ -58,6 +58,9 @@ def case(request):
 
 
 def test_budget_branches():
+    tiles = np.zeros(3, np.int32)
+    nat.call("h2o_shap_tiles", tiles.ctypes.data)       # the Python constants mirror the compiled ones
+    assert tiles.tolist() == [shap.ROW_TILE, shap.X_TILE_BYTES, shap.PHI_TILE_BYTES]
     F33, F70 = 33, 70
     assert F33 * R * 4 <= shap.X_TILE_BYTES < F70 * R * 4
     assert R * 1 * (F33 + 1) * 8 <= shap.PHI_TILE_BYTES < R * 3 * (F33 + 1) * 8
