@@ -256,7 +256,11 @@ class Model:
         return (vm or tm).get("max_f1_threshold", 0.5) if self.model_category == "Binomial" else None
 
     def metrics_for(self, X, y, w=None, offset=None):
-        P = self.score_tensor(X, offset)
+        return self.metrics_from_scores(self.score_tensor(X, offset), y, w)
+
+    def metrics_from_scores(self, P, y, w=None):
+        """The metrics of :meth:`metrics_for` from the prediction matrix ``P`` (:meth:`score_tensor`,
+        :meth:`score_from_raw`) of rows that were scored already."""
         cat = self.model_category
         if cat in ("Binomial", "Multinomial", "Regression"):
             return mm.make_metrics(cat, y.to(P.device), P, None if w is None else w.to(P.device),

@@ -8,6 +8,9 @@ A :class:`Tree` is a flat node table (root = 0): ``feat`` (-1 = leaf), raw-value
 HIP kernel ``k_predict`` of ``csrc/predict_kernels.hip`` (CUDA tensors) or a vectorised PyTorch traversal (CPU).
 :meth:`Forest.predict_raw_grid` scores the rows once per grid tuple of a feature set (partial dependence,
 ``explain.py``): ``k_predict_grid`` of ``csrc/pdp_kernels.hip`` on CUDA tensors, overwrite-and-rescore on CPU.
+:meth:`Forest.predict_raw_permuted` scores them once per shuffled feature (permutation importance,
+``rapids._permutation_varimp``): ``k_predict_permuted`` of ``csrc/permute_kernels.hip`` on CUDA tensors, clone,
+overwrite and re-score on CPU.
 """
 from __future__ import annotations
 
@@ -35,10 +38,15 @@ nat.register_hip_signatures({
     # X, N, K, forest, sel, V, G, masks, featx, ws_chunks, out, stream
     "h2o_predict_grid": [nat.c_void_p, nat.c_ll, nat.c_int, _view_p] + [nat.c_void_p] * 2 + [nat.c_ll]
                         + [nat.c_void_p] * 2 + [nat.c_int] + [nat.c_void_p] * 2,
+    # X, N, K, F, forest, feats, src, J, fmask, chunk, max_chunks, out, stream
+    "h2o_predict_permuted": [nat.c_void_p, nat.c_ll, nat.c_int, nat.c_int, _view_p] + [nat.c_void_p] * 2 + [nat.c_ll]
+                            + [nat.c_void_p] + [nat.c_int] * 2 + [nat.c_void_p] * 2,
 })
 
 PD_CHUNK = 64               # grid tuples per chunk of k_predict_grid (PD_CHUNK in csrc/pdp_kernels.hip)
 PD_MASK_BYTES = 64 << 20    # node masks of the chunks of one launch: 8 bytes per (chunk, node)
+PV_CHUNK = 16               # variants per chunk of k_predict_permuted (1 ... 64; measured: profiles/permvi_gpu.md)
+PV_LAUNCH_CHUNKS = 65535    # chunks per launch of k_predict_permuted (grid y); further chunks go in further launches
 
 
 @dataclass
@@ -325,6 +333,65 @@ class Forest:
         featx = torch.empty(n_nodes, dtype=torch.int32, device=X.device)
         nat.call("h2o_predict_grid", Xc.data_ptr(), N, self.K, fl["view"], sel.data_ptr(), Vc.data_ptr(), G,
                  masks.data_ptr(), featx.data_ptr(), ws_chunks, out.data_ptr(), nat.stream_ptr(X.device))
+        return out
+
+    def predict_raw_permuted(self, X: torch.Tensor, feats, src, t0: int = 0, t1: int | None = None,
+                             out: torch.Tensor | None = None) -> torch.Tensor:
+        """:meth:`predict_raw` of X once per variant: variant ``j`` sees ``X[feats[j]][src[j, i]]`` in place of
+        ``X[feats[j]][i]`` (permutation importance, ``rapids._permutation_varimp``). X: float32 [F, N]; ``feats``: J
+        feature indices in [0, F), repeats allowed; ``src``: integer [J, N] on X's device or the host, every entry in
+        [0, N) (a row need not be a permutation; it is converted to int32). Returns [J, N, K] float32 on X's
+        device, cell ``(j, i, c)`` bit-equal to ``predict_raw`` of a clone of X whose row ``feats[j]`` is
+        ``X[feats[j]][src[j]]``. CUDA tensors run the forking walk of ``csrc/permute_kernels.hip`` (no copy of X, one
+        extra sub-walk per variant that leaves the row's own path); CPU tensors clone, overwrite and re-score.
+        ``out``: as in :meth:`predict_raw_grid`, at least ``J * N * K`` elements."""
+        t1 = len(self.trees) if t1 is None else t1
+        F, N = X.shape
+        feats = [int(f) for f in feats]
+        J = len(feats)
+        if any(f < 0 or f >= F for f in feats):
+            raise ValueError(f"feats must be indices in [0, {F}), got {feats}")
+        src = torch.as_tensor(src)
+        if src.dtype.is_floating_point or src.dtype.is_complex or src.dtype == torch.bool:
+            raise ValueError(f"src must be an integer tensor, got {src.dtype}")
+        if tuple(src.shape) != (J, N):
+            raise ValueError(f"src must have shape {(J, N)}, got {tuple(src.shape)}")
+        src = src.to(X.device)
+        if src.numel():         # one reduction, one host read: the kernel reads X[feats[j]][src[j, i]] unguarded
+            lo, hi = torch.stack(torch.aminmax(src)).tolist()
+            if lo < 0 or hi >= N:
+                raise ValueError(f"src must hold row indices in [0, {N}), got [{lo}, {hi}]")
+        if out is None:
+            out = torch.empty(J, N, self.K, dtype=torch.float32, device=X.device)
+        elif (out.dtype != torch.float32 or out.device != X.device or not out.is_contiguous()
+              or out.numel() < J * N * self.K):
+            raise ValueError(f"out must be a contiguous float32 tensor of >= {J * N * self.K} elements on {X.device}")
+        else:
+            out = out.view(-1)[:J * N * self.K].view(J, N, self.K)
+        nt = t1 - t0
+        if nt <= 0 or N == 0 or J == 0:
+            return out.zero_()
+        if not X.is_cuda:
+            Xp = X.float().clone()
+            for j, f in enumerate(feats):
+                Xp[f] = X[f][src[j].long()]
+                out[j] = self.predict_raw(Xp, t0, t1)
+                Xp[f] = X[f]
+            return out
+        fl = self._device_flat(X.device, t0, t1)
+        if fl["n_features"] > F:
+            raise ValueError(f"the forest splits on feature {fl['n_features'] - 1}, X has {F} rows")
+        if N >= 1 << 31:
+            raise ValueError(f"int32 row indices: N = {N} must be below 2^31")
+        Xc, srcc = X.contiguous().float(), src.to(torch.int32).contiguous()
+        chunk = max(1, min(int(PV_CHUNK), 64))
+        fmask = np.zeros(((J + chunk - 1) // chunk, F), dtype=np.uint64)    # bit b of [c][f]: variant c * chunk + b shuffles f
+        for j, f in enumerate(feats):
+            fmask[j // chunk, f] |= np.uint64(1) << np.uint64(j % chunk)
+        fmask = torch.from_numpy(fmask.view(np.int64)).to(X.device)
+        fe = torch.tensor(feats, dtype=torch.int32).to(X.device)
+        nat.call("h2o_predict_permuted", Xc.data_ptr(), N, self.K, F, fl["view"], fe.data_ptr(), srcc.data_ptr(), J,
+                 fmask.data_ptr(), chunk, int(PV_LAUNCH_CHUNKS), out.data_ptr(), nat.stream_ptr(X.device))
         return out
 
     @staticmethod

@@ -9,6 +9,7 @@ device-resident :class:`H2OFrame` implementation, so Rapids munging runs on the 
 from __future__ import annotations
 
 import math
+import os
 import re
 
 import numpy as np
@@ -801,9 +802,24 @@ def _reset_threshold(m, t):
     return [float(old) if old is not None else float("nan")]
 
 
+PERMVI_CHUNK_BYTES = 256 << 20  # margins [Jc, N, K] fp32 + row indices [Jc, N] int32 of one chunk of variants
+
+
+def _permvi_on_device(m, X) -> bool:
+    """The permuted-forest kernel path: a CUDA model matrix, a Binomial / Multinomial / Regression model that
+    scores from forest margins, rows not sharded over ranks, N < 2^31 (int32 row indices), no ``H2O_PERMVI_HIP=0``."""
+    from .parallel import collectives as coll
+    ok = getattr(m, "scores_from_raw", None)
+    return bool(X.is_cuda and os.environ.get("H2O_PERMVI_HIP", "1") != "0" and ok is not None and ok()
+                and m.model_category in ("Binomial", "Multinomial", "Regression") and not coll.is_dist()
+                and X.shape[1] < 1 << 31)
+
+
 def _permutation_varimp(m, frame, metric="AUTO", n_repeats=1, seed=-1):
     """Permutation importance (hex/PermutationVarImp.java): metric degradation when one predictor's values
-    are shuffled; returns a frame of (Variable, Relative, Scaled, Percentage)."""
+    are shuffled; returns a frame of (Variable, Relative, Scaled, Percentage). A tree model on a CUDA device takes
+    the margins of every shuffled matrix from ``Forest.predict_raw_permuted`` (:func:`_permvi_on_device`); the
+    permutations, and so the table for a given seed, are the same on both paths."""
     obj = _model_obj(m)
     X, off = frame.model_matrix(obj.info, device=obj.device)
     y = frame.response_tensor(obj.info, device=obj.device)
@@ -814,16 +830,36 @@ def _permutation_varimp(m, frame, metric="AUTO", n_repeats=1, seed=-1):
     b0 = float(base.get(mname) if hasattr(base, "get") else base[mname])
     g = torch.Generator(device="cpu").manual_seed(seed if seed >= 0 else 1234)
     imp = []
-    for j in range(X.shape[0]):
-        acc = 0.0
-        for _ in range(max(1, n_repeats)):
-            Xp = X.clone()
-            perm = torch.randperm(X.shape[1], generator=g).to(X.device)
-            Xp[j] = X[j][perm]
-            mv = obj.metrics_for(Xp, y, None, off)
-            v = float(mv.get(mname) if hasattr(mv, "get") else mv[mname])
-            acc += (b0 - v) if higher else (v - b0)
-        imp.append(acc / max(1, n_repeats))
+    reps = max(1, n_repeats)
+    if _permvi_on_device(obj, X):
+        # the same permutations in the same order (feature-major, repeats inner), the margins of a chunk of
+        # variants from one pass of Forest.predict_raw_permuted instead of a clone of X and a forest walk each
+        F, N = X.shape
+        step = max(1, PERMVI_CHUNK_BYTES // max(1, N * (obj.forest.K + 1) * 4))
+        vals = []
+        for v0 in range(0, F * reps, step):
+            feats = [v // reps for v in range(v0, min(v0 + step, F * reps))]
+            src = torch.stack([torch.randperm(N, generator=g).to(torch.int32) for _ in feats]).to(X.device)
+            raw = obj.forest.predict_raw_permuted(X, feats, src)
+            for k in range(len(feats)):
+                mv = obj.metrics_from_scores(obj.score_from_raw(raw[k], off), y, None)
+                vals.append(float(mv.get(mname) if hasattr(mv, "get") else mv[mname]))
+        for j in range(F):
+            acc = 0.0
+            for v in vals[j * reps:(j + 1) * reps]:
+                acc += (b0 - v) if higher else (v - b0)
+            imp.append(acc / reps)
+    else:
+        for j in range(X.shape[0]):
+            acc = 0.0
+            for _ in range(reps):
+                Xp = X.clone()
+                perm = torch.randperm(X.shape[1], generator=g).to(X.device)
+                Xp[j] = X[j][perm]
+                mv = obj.metrics_for(Xp, y, None, off)
+                v = float(mv.get(mname) if hasattr(mv, "get") else mv[mname])
+                acc += (b0 - v) if higher else (v - b0)
+            imp.append(acc / reps)
     imp = np.maximum(np.asarray(imp), 0.0)
     mx, tot = max(imp.max(), 1e-300), max(imp.sum(), 1e-300)
     order = np.argsort(-imp, kind="stable")
