@@ -2829,11 +2829,17 @@ __global__ __launch_bounds__(256) void k_amax(const float* __restrict__ aux, lon
 }
 
 // folds the AMAX_SHARDS per-shard maxima, then derives the fixed-point scales
-//   qs = [sa, sb, 1/sa, 1/sb, sp, 1/sp, sn, sd, 1/sn, 1/sd]
-// sa, sb: 2^40 / max (per-block int64 LDS histograms); sp: 2^30 / max|wY| (packed count|wY);
+//   qs = [sa, sb, 1/sa, 1/sb, sp, 1/sp, sn, sd, 1/sn, 1/sd, sw, 1/sw, field shift]
+// sa, sb: 2^40 / max (per-block int64 LDS histograms); sp: 2^30 / max|wY| (packed count|wY; FPACK: sp, sw below);
 // sn, sd: 2^lb / max with 2^lb * N < 2^62 (whole-tree int64 leaf sums cannot overflow).
+// Every scale is min(nominal, QS_CAP = 2^127): the kernels multiply in fp32 by (float)scale, and a nominal scale
+// past FLT_MAX (max below ~3e-27 for 2^40 / max, ~3e-30 for sp, 2^(lb - 128) for the leaf scales) became inf, so
+// every row converted to a saturated integer (NaN for a zero row). A smaller scale keeps |v * scale| inside the
+// field (|v| <= max), its quantum is 2^-127 per row, and a plane with max >= 2^-80 (2^(lb - 127) for the leaf
+// scales, i.e. 2^-80 from 8192 rows on) gets the nominal scale, bit for bit.
 // Also the tree's start-of-build reset: leaf counters and the amax shards themselves once read (the next
 // tree's fused step re-fills them).
+#define QS_CAP 1.7014118346046923e38   // 2^127, the largest power of two that is a finite float
 __global__ __launch_bounds__(256) void k_qscale(unsigned* __restrict__ amax_bits, double* __restrict__ qs,
                                                 int* __restrict__ counters, long long N, int fpack) {
   __shared__ unsigned sm[4];
@@ -2848,15 +2854,16 @@ __global__ __launch_bounds__(256) void k_qscale(unsigned* __restrict__ amax_bits
     const double m = (double)__uint_as_float(sm[c]);
     const bool ok = m > 0.0 && m == m && m < 1e300;
     if (c < 2) {
-      const double sc = ok ? 1099511627776.0 / m : 1.0;   // 2^40 / max
+      const double sc = ok ? fmin(1099511627776.0 / m, QS_CAP) : 1.0;   // 2^40 / max
       qs[c] = sc;
       qs[2 + c] = 1.0 / sc;
       if (c == 1) {                                        // packed wY: 2^30 / max (FPACK: 32-bit field)
-        const double sp = !ok ? 1.0 : fpack ? 0.99 * 2147483648.0 / ((double)PACK_MAX * m) : 1073741824.0 / m;
+        const double sp = !ok ? 1.0
+                          : fmin(fpack ? 0.99 * 2147483648.0 / ((double)PACK_MAX * m) : 1073741824.0 / m, QS_CAP);
         qs[4] = sp;
         qs[5] = 1.0 / sp;
       } else {                                             // packed weight field: scale, 1 / scale, shift
-        const double sw = (fpack && ok) ? 0.99 * 4294967296.0 / ((double)PACK_MAX * m) : 1.0;
+        const double sw = (fpack && ok) ? fmin(0.99 * 4294967296.0 / ((double)PACK_MAX * m), QS_CAP) : 1.0;
         qs[10] = sw;
         qs[11] = 1.0 / sw;
         qs[12] = fpack ? 32.0 : (double)PACK_SHIFT;
@@ -2865,7 +2872,7 @@ __global__ __launch_bounds__(256) void k_qscale(unsigned* __restrict__ amax_bits
       int lb = 61;
       for (long long n = N; n > 0; n >>= 1) --lb;          // 2^lb * N < 2^62
       if (lb < 8) lb = 8;
-      const double sc = ok ? ldexp(1.0, lb) / m : 1.0;
+      const double sc = ok ? fmin(ldexp(1.0, lb) / m, QS_CAP) : 1.0;
       qs[6 + (c - 2)] = sc;
       qs[8 + (c - 2)] = 1.0 / sc;
     }

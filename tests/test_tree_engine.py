@@ -146,10 +146,13 @@ def test_gpu_many_features_path():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("grid", [4, 256])
+@pytest.mark.parametrize("grid", [1, 3, 4, 256])
 def test_gpu_packed_histograms_match_unpacked(grid):
-    # packed (count<<48 | wY) single-atomic LDS histograms == two-atomic int64 histograms; grid=4 makes every
-    # block stream > PACK_MAX rows so the packed flush window is exercised
+    # packed (count<<48 | wY) single-atomic LDS histograms == two-atomic int64 histograms. The packed flush window
+    # is PACK_MAX = 63,488 rows = 31 tiles of 2,048, and 200,000 rows are 98 tiles: grid=1 (98 tiles in one block,
+    # four windows) and grid=3 (33 tiles per block, two windows) stream more than a window per block, so a block
+    # flushes again into the partial it stored before (flush_partial's acc branch); grid=4 (25 tiles = 51,200 rows
+    # per block) and grid=256 stay inside one window
     X, y, info = _data(N=200000, cat=True, seed=9)
     b = fit_binning(X, info.iscat, info.nlevels, max_bins=255)
     dev = torch.device("cuda", 0)
