@@ -102,12 +102,20 @@ __global__ __launch_bounds__(256) void k_kmeans_step(const float* __restrict__ X
 
 extern "C" {
 
+// Most dynamic LDS a block of the two kernels may ask for: all of a gfx950 CU's 160 KiB, which is also the device's
+// per-block limit (hipDeviceProp_t::sharedMemPerBlock = 163840); the HIP runtime needs no opt-in attribute for a
+// dynamic size above 64 KiB (tests/test_kmeans_lloyd_gpu.py launches up to 163744 B). ops/dense.py holds the same
+// figure.
+#define KM_LDS_MAX (160 * 1024)
+
+int h2o_kmeans_lds_limit() { return KM_LDS_MAX; }
+
 int h2o_kmeans_lds_bytes(int K, int P) { return (K * P + 256 * (P + 1)) * 4; }
 
 int h2o_kmeans_assign(const float* X, long long N, int P, const float* C, int K, int* assign, float* mind,
                       hipStream_t stream) {
   const size_t lds = (size_t)(K * P + 256 * (P + 1)) * 4;
-  if (lds > 160 * 1024 || N <= 0) return (int)hipErrorInvalidValue;
+  if (lds > KM_LDS_MAX || N <= 0) return (int)hipErrorInvalidValue;
   const int grid = (int)((N + 255) / 256);
   hipLaunchKernelGGL(k_kmeans_assign, dim3(grid), dim3(256), lds, stream, X, (int64_t)N, P, C, K, assign, mind);
   return (int)hipGetLastError();
@@ -116,7 +124,7 @@ int h2o_kmeans_assign(const float* X, long long N, int P, const float* C, int K,
 int h2o_kmeans_step(const float* X, long long N, int P, const float* C, int K, const float* w, int* assign, float* mind,
                     float* slab, hipStream_t stream) {
   const size_t lds = (size_t)(K * P + 256 * (P + 1) + 512) * 4;
-  if (lds > 160 * 1024 || N <= 0) return (int)hipErrorInvalidValue;
+  if (lds > KM_LDS_MAX || N <= 0) return (int)hipErrorInvalidValue;
   const int grid = (int)((N + 255) / 256);
   hipLaunchKernelGGL(k_kmeans_step, dim3(grid), dim3(256), lds, stream, X, (int64_t)N, P, C, K, w, assign, mind, slab);
   return (int)hipGetLastError();

@@ -21,6 +21,8 @@ nat.register_hip_signatures({
     "h2o_bias_act_bwd": [nat.c_void_p, nat.c_void_p, nat.c_void_p, nat.c_void_p, nat.c_ll, nat.c_int, nat.c_int,
                          nat.ctypes.c_float, nat.c_ull, nat.c_void_p, nat.c_int, nat.c_void_p],
     "h2o_kmeans_assign": [nat.c_void_p, nat.c_ll, nat.c_int, nat.c_void_p, nat.c_int, nat.c_void_p, nat.c_void_p, nat.c_void_p],
+    "h2o_kmeans_lds_limit": [],
+    "h2o_kmeans_lds_bytes": [nat.c_int, nat.c_int],
     "h2o_kmeans_step": [nat.c_void_p, nat.c_ll, nat.c_int, nat.c_void_p, nat.c_int, nat.c_void_p, nat.c_void_p,
                         nat.c_void_p, nat.c_void_p, nat.c_void_p],
     "h2o_adadelta": [nat.c_void_p, nat.c_void_p, nat.c_void_p, nat.c_void_p, nat.c_ll, nat.c_ll, nat.ctypes.c_float,
@@ -230,6 +232,7 @@ def _mfma_shape(K, P):
     return (out[0], out[1], out[2]) if ok else None
 
 
+_KM_LDS_MAX = 160 * 1024   # dynamic-LDS bytes a block of the scalar kernels may use (csrc/kmeans_kernels.hip: KM_LDS_MAX)
 _KM_GRID: dict = {}     # (K, P) -> blocks of one resident round of the MFMA Lloyd kernel (occupancy query, cached)
 
 
@@ -260,7 +263,7 @@ def kmeans_step(X: torch.Tensor, C: torch.Tensor, w: torch.Tensor | None = None,
                  0 if a is None else a.data_ptr(), d.data_ptr(), slab.data_ptr(), grid, nat.stream_ptr(X.device))
         tot = slab.sum(0, dtype=torch.float64)
         return (a.long() if a is not None else None), d, tot[:K, :P].contiguous(), tot[:K, P].contiguous()
-    if X.is_cuda and (K * P + 256 * (P + 1) + 512) * 4 <= 160 * 1024 and N > 0 and K * (P + 1) <= 8192:
+    if X.is_cuda and (K * P + 256 * (P + 1) + 512) * 4 <= _KM_LDS_MAX and N > 0 and K * (P + 1) <= 8192:
         X = X.contiguous().float()
         C = C.contiguous().float()
         wf = None if w is None else w.contiguous().float()
@@ -321,7 +324,7 @@ def kmeans_assign(X: torch.Tensor, C: torch.Tensor):
     """Closest center and squared distance for every row. X [N, P], C [K, P] float32."""
     N, P = X.shape
     K = C.shape[0]
-    if X.is_cuda and (K * P + 256 * (P + 1)) * 4 <= 160 * 1024 and N > 0:
+    if X.is_cuda and (K * P + 256 * (P + 1)) * 4 <= _KM_LDS_MAX and N > 0:
         X = X.contiguous().float()
         C = C.contiguous().float()
         a = torch.empty(N, dtype=torch.int32, device=X.device)
