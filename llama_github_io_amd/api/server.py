@@ -686,11 +686,30 @@ def create_app(client_disconnect_timeout: float | None = None, login=None):
         return dict(models=[_model_json(m)])
 
     # ---- predictions & metrics
+    def _scored(m, fr, p):
+        """The frame a Predictions request asks for: the h2o-py client sets ``leaf_node_assignment`` (with
+        ``leaf_node_assignment_type``) for predict_leaf_node_assignment, ``predict_staged_proba`` for
+        staged_predict_proba, ``feature_frequencies`` for feature_frequencies; none of them: the predictions."""
+        from h2o.model_api import ModelBaseAPI
+
+        class Api(ModelBaseAPI):
+            algo = m.algo
+
+            def _m(self):
+                return m
+        if p.get("leaf_node_assignment") is True:
+            return Api().predict_leaf_node_assignment(fr, _unquote(p.get("leaf_node_assignment_type")) or "Path")
+        if p.get("predict_staged_proba") is True:
+            return Api().staged_predict_proba(fr)
+        if p.get("feature_frequencies") is True:
+            return Api().feature_frequencies(fr)
+        return m.predict(fr)
+
     @app.post("/3/Predictions/models/{mid}/frames/{fid}")
     async def predict(mid: str, fid: str, request: Request):
         p = await _params(request)
         m, fr = _get_model(mid), _get_frame(fid)
-        pred = m.predict(fr)
+        pred = _scored(m, fr, p)
         dest = _unquote(p.get("predictions_frame"))
         if dest:
             dkv.remove(pred.frame_id)
@@ -705,7 +724,8 @@ def create_app(client_disconnect_timeout: float | None = None, login=None):
         return {"__meta": v3.meta("ModelMetricsListSchemaV3", "ModelMetricsList"), "model": v3.model_key(mid),
                 "frame": v3.frame_key(fid), "predictions_frame": v3.frame_key(pred.frame_id),
                 "model_metrics": [mm] if mm else [], "deviances_frame": None, "reconstruction_error": False,
-                "leaf_node_assignment": False, "exemplar_index": -1, "deep_features_hidden_layer": -1}
+                "leaf_node_assignment": p.get("leaf_node_assignment") is True, "exemplar_index": -1,
+                "deep_features_hidden_layer": -1}
 
     @app.post("/4/Predictions/models/{mid}/frames/{fid}")
     async def predict4(mid: str, fid: str, request: Request):
@@ -715,7 +735,7 @@ def create_app(client_disconnect_timeout: float | None = None, login=None):
         job = Job("Predictions", dest=dest)
 
         def run():
-            pred = m.predict(fr)
+            pred = _scored(m, fr, p)
             dkv.remove(pred.frame_id)
             pred.frame_id = dest
             dkv.put(dest, pred)

@@ -19,7 +19,7 @@ from ..ops import tree as T
 from .base import DataInfo
 from ..parallel.order_stats import global_quantile
 from .distributions import ORDER_STAT_DISTS, get_distribution
-from .shared_tree import SharedTreeModel, SharedTreeTrainer
+from .shared_tree import SharedTreeModel, SharedTreeTrainer, stages_on_device
 from ..ops.segment import segment_sum
 
 _FUSED_DIST = {"gaussian": 0, "bernoulli": 1, "quasibinomial": 2, "poisson": 3, "gamma": 4, "tweedie": 5,
@@ -82,11 +82,45 @@ class GBMModel(SharedTreeModel):
                                 huber_alpha=self.params.get("huber_alpha", 0.9),
                                 custom_distribution_func=self.params.get("custom_distribution_func"))
 
+    def _staged_margins(self, X):
+        """[n, N, K]: the raw margins of iterations 1 .. n, for every n, from one walk of the forest
+        (``Forest.predict_stages``; slice n - 1 is bit-equal to ``_raw(X, ntrees=n)``), or with ``H2O_STAGES_HIP=0``
+        from one ``_raw`` call per n."""
+        nb, K = self.ntrees_built(), self._trees_per_iter()
+        if not stages_on_device():
+            return torch.stack([self._raw(X, ntrees=n) for n in range(1, nb + 1)]) if nb else \
+                torch.zeros(0, X.shape[1], K, device=X.device)
+        st = self.forest.predict_stages(X, 0, nb * K)              # [nb * K, N]
+        if K == 1:
+            return st.view(nb, -1, 1)
+        cls = torch.as_tensor(self.forest.tree_class[:nb * K], device=st.device).view(nb, K)
+        # iteration n's tree of class c sits at position argsort(cls[n])[c] of the iteration
+        M = torch.gather(st.view(nb, K, -1), 1, cls.argsort(1)[:, :, None].expand(nb, K, st.shape[1]))
+        return M.permute(0, 2, 1).contiguous()
+
     def staged_predict_proba(self, X):
-        out = []
-        for n in range(1, self.ntrees_built() + 1):
-            out.append(self._raw(X, ntrees=n))
-        return out
+        """The raw margins [N, K] of iterations 1 .. n, one list entry per n."""
+        return list(self._staged_margins(X))
+
+    def staged_predict_proba_frame(self, frame):
+        """One column ``T{n}.C{c}`` per tree in forest order: the model's response from the margins of iterations
+        1 .. n through the same ``init_f``, offset and link as ``predict`` (regression: the prediction; binomial:
+        the probability of the first response level; multinomial: class c's probability). One forest walk, the link
+        applied over all stages at once."""
+        from ..frame import Column, H2OFrame
+        X, offset = frame.model_matrix(self.info, device=self.device)
+        M = self._staged_margins(X)
+        nb, N, K = M.shape
+        names = self.stage_column_names()
+        if nb == 0:
+            return H2OFrame._from_columns([])
+        off = None if offset is None else offset.to(M.device).repeat(nb)
+        P = self.score_from_raw(M.view(nb * N, K), off)          # _response_from_raw and predict's class balancing
+        # regression: [n * N]; binomial: [n * N, 2], column 0 = the first response level; multinomial: [n * N, K]
+        P = P.view(nb, N, -1)
+        cls = self.forest.tree_class
+        return H2OFrame._from_columns([Column(names[n * K + j], "real", P[n, :, cls[n * K + j]].double().contiguous())
+                                       for n in range(nb) for j in range(K)])
 
 
 class GBMTrainer(SharedTreeTrainer):

@@ -37,6 +37,12 @@ SHARED_TREE_DEFAULTS = dict(
 _CANCEL_EVERY = 4     # trees between cancellation checks of a REST job
 
 
+def stages_on_device() -> bool:
+    """``H2O_STAGES_HIP=0`` restores the code paths from before ``Forest.predict_stages``: one forest pass per stage
+    of ``staged_predict_proba``, the NumPy walk of ``feature_frequencies``."""
+    return os.environ.get("H2O_STAGES_HIP", "1") != "0"
+
+
 def resolve_seed(seed) -> int:
     if seed is None or int(seed) == -1:
         from ..parallel import collectives as coll
@@ -82,6 +88,46 @@ class SharedTreeModel(Model):
     def predict_leaf_node_assignment(self, X: torch.Tensor) -> torch.Tensor:
         _, leaves = self.forest.predict_raw(X.to(self.device), return_leaves=True)
         return leaves
+
+    def stage_column_names(self) -> list:
+        """``T{n}.C{c}`` per tree in forest order: n = the tree's 1-based index among the trees of its class, c = its
+        1-based class."""
+        seen, names = {}, []
+        for c in self.forest.tree_class:
+            seen[c] = seen.get(c, 0) + 1
+            names.append(f"T{seen[c]}.C{c + 1}")
+        return names
+
+    def predict_leaf_node_assignment_frame(self, frame, type="Path"):
+        """One column per tree: the leaf each row reaches, as its ``L`` / ``R`` decision string from the root
+        (``type="Path"``, an enum column whose domain is the sorted set of the paths that occur) or as the leaf's
+        id in ``h2o.tree.H2OTree``'s numbering (``type="Node_ID"``, an int column). One forest walk
+        (``Forest.predict_stages``), then device gathers through the per-forest tables of ``Forest.leaf_tables``:
+        no string is built per row."""
+        from ..frame import Column, H2OFrame
+        from ..parallel import dframe
+        if type not in ("Path", "Node_ID"):
+            raise ValueError(f"type must be 'Path' or 'Node_ID', got {type!r}")
+        X, _ = frame.model_matrix(self.info, device=self.device)
+        leaves = self.forest.predict_stages(X, stage=False, leaves=True).long()
+        tabs = self.forest.leaf_tables(X.device)
+        cols = []
+        for t, name in enumerate(self.stage_column_names()):
+            if type == "Node_ID":
+                cols.append(Column(name, "int", tabs["node_id"][leaves[t]].double()))
+                continue
+            rank = tabs["path_rank"][leaves[t]]
+            present = torch.unique(rank)                       # sorted: ranks follow the sorted paths
+            codes = torch.searchsorted(present, rank).to(torch.int32)
+            domain = [tabs["paths"][t][r] for r in present.tolist()]
+            if dframe.current_ctx() is not None:               # a sharded frame: one domain on every rank
+                codes, domain = dframe.unify_domain(codes, domain)
+            cols.append(Column(name, "enum", codes.to(torch.int32), domain))
+        return H2OFrame._from_columns(cols)
+
+    def feature_frequencies_tensor(self, X: torch.Tensor) -> torch.Tensor:
+        """int32 [N, F]: per row and feature, how many split nodes on the row's prediction paths split on it."""
+        return self.forest.predict_stages(X.to(self.device), stage=False, freq=True).T
 
     def update_tree_weights(self, frame, weights_column):
         """Recompute every node's weight (``cover``, used by TreeSHAP and the tree API) from the rows of

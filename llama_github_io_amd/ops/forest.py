@@ -11,6 +11,9 @@ HIP kernel ``k_predict`` of ``csrc/predict_kernels.hip`` (CUDA tensors) or a vec
 :meth:`Forest.predict_raw_permuted` scores them once per shuffled feature (permutation importance,
 ``rapids._permutation_varimp``): ``k_predict_permuted`` of ``csrc/permute_kernels.hip`` on CUDA tensors, clone,
 overwrite and re-score on CPU.
+:meth:`Forest.predict_stages` gives the per-tree and per-feature by-products of one walk (staged margins, leaf
+assignments, feature frequencies): ``k_forest_stages`` of ``csrc/forest_stages_kernels.hip`` on CUDA tensors, a
+per-tree PyTorch loop on CPU.
 """
 from __future__ import annotations
 
@@ -41,12 +44,16 @@ nat.register_hip_signatures({
     # X, N, K, F, forest, feats, src, J, fmask, chunk, max_chunks, out, stream
     "h2o_predict_permuted": [nat.c_void_p, nat.c_ll, nat.c_int, nat.c_int, _view_p] + [nat.c_void_p] * 2 + [nat.c_ll]
                             + [nat.c_void_p] + [nat.c_int] * 2 + [nat.c_void_p] * 2,
+    # X, N, K, F, forest, freq_lds_bytes, stage, leaf, freq, stream
+    "h2o_forest_stages": [nat.c_void_p, nat.c_ll, nat.c_int, nat.c_int, _view_p, nat.c_int] + [nat.c_void_p] * 4,
 })
 
 PD_CHUNK = 64               # grid tuples per chunk of k_predict_grid (PD_CHUNK in csrc/pdp_kernels.hip)
 PD_MASK_BYTES = 64 << 20    # node masks of the chunks of one launch: 8 bytes per (chunk, node)
 PV_CHUNK = 16               # variants per chunk of k_predict_permuted (1 ... 64; measured: profiles/permvi_gpu.md)
 PV_LAUNCH_CHUNKS = 65535    # chunks per launch of k_predict_permuted (grid y); further chunks go in further launches
+STAGES_FREQ_LDS_BYTES = 16 << 10    # k_forest_stages counts feature frequencies in LDS while F * 256 bytes fit under
+                                    # this (F <= 64: at least 10 waves per CU), in the output array itself past it
 
 
 @dataclass
@@ -394,8 +401,114 @@ class Forest:
                  fmask.data_ptr(), chunk, int(PV_LAUNCH_CHUNKS), out.data_ptr(), nat.stream_ptr(X.device))
         return out
 
+    def predict_stages(self, X: torch.Tensor, t0: int = 0, t1: int | None = None, *, stage: bool = True,
+                       leaves: bool = False, freq: bool = False, out: torch.Tensor | None = None):
+        """The per-tree and per-feature by-products of ONE walk of the trees ``[t0, t1)`` over X (float32 [F, N]),
+        tree-major so that a column of a result frame is one contiguous row. ``stage``: float32 [T, N], cell
+        ``(t, i)`` = the fp32 sum in forest order of the leaf values of the trees ``t' <= t`` of tree ``t``'s class,
+        bit-equal to ``predict_raw(X, t0, t0 + t + 1)[i, cls[t]]``; ``leaves``: int32 [T, N], what
+        ``predict_raw(..., return_leaves=True)`` gives, transposed; ``freq``: int32 [F, N], the number of split nodes
+        on row i's T paths that split on feature f. Returns the requested tensors on X's device in that order (one
+        tensor when one is asked for, else a tuple). CUDA tensors run ``k_forest_stages``
+        (``csrc/forest_stages_kernels.hip``); CPU tensors a per-tree loop over :meth:`_predict_torch`.
+        ``out`` (for ``stage``): as in :meth:`predict_raw_grid`, at least ``T * N`` elements."""
+        t1 = len(self.trees) if t1 is None else t1
+        F, N = X.shape
+        T = max(t1 - t0, 0)
+        if not (stage or leaves or freq):
+            raise ValueError("predict_stages: ask for at least one of stage, leaves, freq")
+        if out is not None and not stage:
+            raise ValueError("out= is the buffer of stage")
+        st = lv = fq = None
+        if stage:
+            if out is None:
+                st = torch.empty(T, N, dtype=torch.float32, device=X.device)
+            elif (out.dtype != torch.float32 or out.device != X.device or not out.is_contiguous()
+                  or out.numel() < T * N):
+                raise ValueError(f"out must be a contiguous float32 tensor of >= {T * N} elements on {X.device}")
+            else:
+                st = out.view(-1)[:T * N].view(T, N)
+        if leaves:
+            lv = torch.empty(T, N, dtype=torch.int32, device=X.device)
+        if freq:
+            fq = torch.empty(F, N, dtype=torch.int32, device=X.device)
+        res = [r for r in (st, lv, fq) if r is not None]
+        ret = res[0] if len(res) == 1 else tuple(res)
+        if T <= 0 or N == 0:
+            for r in res:
+                r.zero_()
+            return ret
+        fl = self._device_flat(X.device, t0, t1)
+        if fl["n_features"] > F:
+            raise ValueError(f"the forest splits on feature {fl['n_features'] - 1}, X has {F} rows")
+        Xc = X.contiguous().float()
+        if X.is_cuda:
+            nat.call("h2o_forest_stages", Xc.data_ptr(), N, self.K, F, fl["view"], int(STAGES_FREQ_LDS_BYTES),
+                     nat.ptr(st), nat.ptr(lv), nat.ptr(fq), nat.stream_ptr(X.device))
+            return ret
+        acc = torch.zeros(N, self.K, dtype=torch.float32)
+        leaf_all = torch.empty(N, T, dtype=torch.int32)
+        self._predict_torch(Xc, fl, T, acc, leaf_all, stages=st)
+        if lv is not None:
+            lv.copy_(leaf_all.T)
+        if fq is not None:
+            # the features on the way to a leaf are fixed by the tree: one table row per node, gathered per tree
+            tab = self._path_feature_counts(fl, F)
+            fq.zero_()
+            for t in range(T):
+                fq += tab[leaf_all[:, t].long()].T
+        return ret
+
+    def leaf_tables(self, device):
+        """Per flat node of the whole forest, for leaf node assignment: ``node_id`` int32 [n_nodes] on ``device``, the
+        node's breadth-first position in its tree (root 0, a split's left child then its right child appended in
+        visiting order: the ids of ``tree_json`` / ``h2o.tree.H2OTree``); ``path_rank`` int32 [n_nodes] on
+        ``device``, for a leaf the rank of its root-to-leaf ``L`` / ``R`` string among its tree's sorted leaf paths
+        (-1 for a split); ``paths``: per tree, that sorted list. Built once on the host, cached with the flat arrays."""
+        key = (str(device), "leaf_tables")
+        if key not in self._flat:
+            ids, ranks, paths = [], [], []
+            for t in self.trees:
+                n = t.n_nodes
+                nid = np.zeros(n, dtype=np.int32)
+                order, i = [0], 0
+                while i < len(order):
+                    k = order[i]
+                    nid[k] = i
+                    if t.feat[k] >= 0:
+                        order += [int(t.left[k]), int(t.right[k])]
+                    i += 1
+                path = [""] * n
+                for k in order:                     # parents come before their children in breadth-first order
+                    if t.feat[k] >= 0:
+                        path[int(t.left[k])] = path[k] + "L"
+                        path[int(t.right[k])] = path[k] + "R"
+                leaf_paths = sorted(path[k] for k in range(n) if t.feat[k] < 0)
+                pos = {p: r for r, p in enumerate(leaf_paths)}
+                ranks.append(np.asarray([pos[path[k]] if t.feat[k] < 0 else -1 for k in range(n)], dtype=np.int32))
+                ids.append(nid)
+                paths.append(leaf_paths)
+            cat = lambda xs: torch.from_numpy(np.concatenate(xs) if xs else np.zeros(0, np.int32)).to(device)
+            self._flat[key] = dict(node_id=cat(ids), path_rank=cat(ranks), paths=paths)
+        return self._flat[key]
+
     @staticmethod
-    def _predict_torch(X, fl, nt, out, leaves):
+    def _path_feature_counts(fl, F):
+        """int32 [n_nodes, F]: per node, how many of its proper ancestors split on each feature."""
+        feat, left, right, roots = (fl[k].cpu().numpy() for k in ("feat", "left", "right", "roots"))
+        cnt = np.zeros((len(feat), F), dtype=np.int32)
+        todo = [int(r) for r in roots]
+        while todo:
+            n = todo.pop()
+            if feat[n] >= 0:
+                for c in (int(left[n]), int(right[n])):
+                    cnt[c] = cnt[n]
+                    cnt[c, feat[n]] += 1
+                    todo.append(c)
+        return torch.from_numpy(cnt)
+
+    @staticmethod
+    def _predict_torch(X, fl, nt, out, leaves, stages=None):
         N = X.shape[1]
         ar = torch.arange(N)
         feat, thr, left, right = fl["feat"].long(), fl["thr"], fl["left"].long(), fl["right"].long()
@@ -422,5 +535,7 @@ class Forest:
                 nxt = torch.where(go, left[node], right[node])
                 node = torch.where(act, nxt, node)
             out[:, int(fl["cls"][t])] += val[node]
+            if stages is not None:
+                stages[t] = out[:, int(fl["cls"][t])]
             if leaves is not None:
                 leaves[:, t] = node.int()
