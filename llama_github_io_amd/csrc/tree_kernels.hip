@@ -8,17 +8,23 @@
 //
 // Design (MI355X-first, not a port):
 //   * features are pre-binned once into a row-major uint8 matrix (bin 255 = NA), so a row is Fp bytes.
-//   * rows are PHYSICALLY partitioned by tree node every level (stable two-pass partition: k_count ->
-//     k_plan scan -> k_move_lean), so every histogram pass streams contiguous rows of ONE node and the
-//     per-node histogram lives privately in LDS (fixed-point int64, see below).
-//   * only the smaller child of each split is histogrammed (k_hist_build over its contiguous rows),
-//     into a COMPACT buffer indexed by the parent (one built child per parent); the sibling comes
-//     from parent - child (fused into k_hist_reduce, or into k_split_find on row-sharded levels), in fp64.
-//     Row-sharded runs exchange only that compact buffer: half the bytes of every child slot of the level.
-//   * split search, child planning, leaf numbering and tile planning all stay on device: a whole
-//     tree is a fixed launch sequence with no host synchronisation.
-//   * rows reaching a leaf write their leaf id in ORIGINAL row order (scatter through ridx) and stop
-//     moving; the prediction update is then a coalesced elementwise op.
+//   * rows are PHYSICALLY regrouped by tree node every SECOND level: k_route moves the rows of an even level
+//     two levels down at once into ping-pong buffers (bins + wY (+ w), no row index), so an even level's
+//     histogram pass streams contiguous rows of ONE node and the per-node histogram lives privately in LDS
+//     (fixed-point int64, see below).
+//   * odd levels are histogrammed from the PARENT's rows through the parent's decision (the filtered pass of
+//     k_hist_build: wave-local queues of the rows that go to the built child); nothing moves for them.
+//   * only the smaller child of each split is histogrammed, into a COMPACT buffer indexed by the parent (one
+//     built child per parent); the sibling comes from parent - child (fused into k_hist_reduce, or into
+//     k_split_find on row-sharded levels), in fp64. Row-sharded runs exchange only that compact buffer: half
+//     the bytes of every child slot of the level.
+//   * split search, child planning, leaf numbering and tile planning all stay on device. The host fills one
+//     TreePlan per tree and makes one call (h2o_tree_all; row-sharded: h2o_tree_dist, with the level
+//     collectives enqueued in between): a fixed launch sequence with no host synchronisation, which the
+//     single-process trainer captures once and replays as a graph.
+//   * rows that reach a leaf stop moving. After the last level k_leaf_assign walks every row of the ORIGINAL
+//     order down the finished tree: leaf ids and leaf sums come from that one coalesced pass, so the
+//     prediction update is an elementwise op.
 //   * wave64: 8 lanes own one row (one 32-bit word = 4 bins each), a wave covers 8 rows, so lanes of a
 //     wave hit 8 different feature sub-histograms (few same-address LDS atomic collisions).
 #include <hip/hip_runtime.h>
@@ -95,7 +101,7 @@ struct SplitParams {
   // other columns -1; the first column's block searches one histogram over all of the group's levels
   const int* gcat;
   // the tree's total weight (written by the root's search), read at depth >= 1: the noise floor of float-weight
-  // histogram entries (see split_find_body); null = none
+  // histogram entries (see k_split_find); null = none
   const double* rootw;
 };
 
@@ -180,7 +186,7 @@ __device__ void block_sum4(double v[4], double* scratch /* >= 4*(BLK/64) */) {
 // Layout (int64), BANK-CONFLICT FREE for the atomics: entry (feature fl, bin) of plane r (0: w or packed,
 // 1: wY) sits at r * HPLANE + bin * FTILE + fslot(fl). A ds_add_u64 wave-instruction is served in four
 // 16-lane groups (2 rows x 8 words, bank = dword address mod 32); each lane adds feature 4*word + k of its
-// row, with k rotated by the row's parity (hist_rows), and fslot() places features 4j+k and 4(j+4)+k two
+// row, with k rotated by the row's parity (hist_span), and fslot() places features 4j+k and 4(j+4)+k two
 // bank pairs apart, so the 16 lanes of a group always hit 16 distinct bank pairs whatever the bins are.
 // (The former [feature][bin] layout put random bins on random banks: 3-4 way conflicts per group.)
 // Plane 1 is offset by 16 entries so the flush's (r = 0, 1) lane pairs read disjoint banks.
@@ -237,10 +243,10 @@ __device__ __forceinline__ void put_partial(P* q, double d, bool acc) {
   *q = acc ? (P)((double)*q + d) : (P)d;
 }
 // srep/snb (LDS, per tile feature): replica count and bin count of a low-cardinality feature whose updates were
-// spread over `srep` copies of its bins (see hist_rows); bin b < nb is the sum of the copies b + c * nb.
+// spread over `srep` copies of its bins (see hist_span); bin b < nb is the sum of the copies b + c * nb.
 __device__ void flush_partial(const long long* h, const float* nayy, double node_wyy, int ftile, int F,
                               double* __restrict__ part, const double* __restrict__ qs, bool packed, bool acc,
-                              bool f32, const int* srep, const int* snb, const int* sfine) {
+                              bool f32, const int* srep, const int* snb) {
   const int f0 = ftile * FTILE;
   const int nf = min(FTILE, F - f0);
   const double inv_a = qs[2], inv_b = qs[3], inv_p = qs[5];
@@ -255,14 +261,7 @@ __device__ void flush_partial(const long long* h, const float* nayy, double node
       if (fl >= nf) { fl -= nf; ++bin; }
       const int reps = srep[fl], nb = snb[fl];
       long long q = 0;
-      if (sfine[fl]) {
-        const int m = fl & ~3, k = fl & 3;
-#pragma unroll
-        for (int l = 0; l < 4; ++l) {
-          const int bb = l <= k ? bin : bin - 1;
-          if (bb >= 0) q += h[bb * FTILE + fslot(m + l)];
-        }
-      } else if (reps == 1) {
+      if (reps == 1) {
         q = h[bin * FTILE + fslot(fl)];
       } else if (bin < nb) {
         for (int c = 0; c < reps; ++c) q += h[(bin + c * nb) * FTILE + fslot(fl)];
@@ -292,17 +291,7 @@ __device__ void flush_partial(const long long* h, const float* nayy, double node
     const int fl = rem >> 1, r = rem & 1;
     const int reps = srep[fl], nb = snb[fl];
     long long q = 0;                       // the entry's fixed-point value (plane r), replicas summed
-    if (sfine[fl]) {
-      // column k of a fine group: bin b holds fine bins t = 4h + l with h + [l > k] == b, i.e. entries
-      // (b, l <= k) and (b - 1, l > k) of the fine histogram (NA: t = 1020 = entry (255, 0))
-      const int m = fl & ~3, k = fl & 3;
-      const int pl = r * HPLANE;
-#pragma unroll
-      for (int l = 0; l < 4; ++l) {
-        const int bb = l <= k ? bin : bin - 1;
-        if (bb >= 0) q += h[pl + bb * FTILE + fslot(m + l)];
-      }
-    } else if (reps == 1 || bin < nb) {
+    if (reps == 1 || bin < nb) {
       for (int c = 0; c < reps; ++c) q += h[r * HPLANE + (bin + c * nb) * FTILE + fslot(fl)];
     }
     const double d = (double)q * (r ? inv_b : inv_a);
@@ -359,17 +348,6 @@ struct RowFilter {
 };
 
 
-// Histogram rows [r0, r1) of one node into LDS: lane group g (8 lanes, one 4-feature row word each)
-// takes rows g, g + RPI, ...; UNR rows per lane group are loaded before any atomic.
-// MEASURED: this loop is VALU-issue bound, not memory bound (prefetching / 4..16 rows in flight all ran
-// within 1.5 %), so everything per-lane is hoisted: the 4 feature slots and byte shifts of the lane's word
-// (rotated by row parity, see the layout note), feature validity, and an all-bytes NA test per word; the
-// common row is then bfe + lshl_add + ds_add_u64 per feature (two atomics when not PACKED).
-// FILT (odd levels): the rows of a parent tile that the parent's decision sends to the built child, as an
-// ascending row list in LDS (one lane per row tests the split byte; wave ballots + a (pass, wave) prefix
-// place them). The histogram loop then runs over full lane groups of selected rows: filtering inside it
-// left about half of each wave's lanes idle through the atomics (the loop is issue-bound), so a filtered
-// pass cost two plain passes. ftile-0 blocks also count the parent's left-goers (nl_out).
 // orders LDS accesses of different lanes of one wave (compiler and hardware), without a block barrier
 __device__ __forceinline__ void wave_sync_lds() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -430,7 +408,7 @@ __device__ __forceinline__ int filt_append(const RowFilter& flt, int r0, int r1,
 
 // Row loads of the histogram loop. BUF: 32-bit buffer offsets into the bins (rows of 2^lgw bytes) and the aux planes
 // (each < 4 GiB; the host checks): one shift per row and per-unroll SGPR offsets instead of a 64-bit multiply-add
-// per load (the loop is VALU-issue bound, see hist_rows).
+// per load (the loop is VALU-issue bound, see hist_span).
 struct HistSrc {
   const unsigned* bins32;
   const float* aw;
@@ -455,149 +433,28 @@ __device__ __forceinline__ HistSrc make_src(const unsigned* bins32, const float*
 // across merged same-node tiles changed nothing (1.376-1.394 vs 1.380-1.388 ms/tree), a 64-VGPR build with two
 // blocks per CU was 13 % slower (spills), 512 / 384 blocks per launch 5-8 % slower (more partials), and spreading
 // low-cardinality features over bin replicas removed the SQ_LDS_ADDR_CONFLICT cycles (1.8e8 -> 5e6) at equal time.
-// Histogram rows [r0, r1) of one node into LDS (FILT: entries [r0, r1) of the LDS row list): lane group g
-// (8 lanes, one 4-feature row word each) takes rows g, g + GR, ...; UNR rows per lane group are loaded
-// before any atomic.
+// hist_span histograms rows [r0, r1) of one node into LDS: lane group g (8 lanes, one 4-feature row word each)
+// takes rows g, g + GR, ...; UNR rows per lane group are loaded before any atomic.
 // MEASURED: this loop is VALU-issue bound, not memory bound (prefetching / 4..16 rows in flight all ran
 // within 1.5 %), so everything per-lane is hoisted: the 4 feature slots and byte shifts of the lane's word
 // (rotated by row parity, see the layout note), feature validity; NONA (no NA bin anywhere, a launch-time
 // property of the bins) drops the per-word NA test at compile time; a batch wholly inside the node skips the
 // per-row bounds tests; BUF addresses with 32-bit offsets. The common row is then bfe + lshl_add + ds_add_u64
-// per feature (two atomics when not PACKED).
-template <bool FILT, bool PACKED, bool UNIT, bool NONA, bool BUF, bool FINE, int GR = RPI, int UNR = H2O_UNR>
-__device__ __forceinline__ void hist_rows(long long* h, float* nayy, const HistSrc& src, int W, int wabs,
-                                          int F, bool lead, int r0, int r1, int g, int j, float& wyy, float sa,
-                                          float sb, float sp, const int* lst, const int* srep, const int* snb,
-                                          const int* sfine) {
-  const int rot = g & 1;
-  unsigned offb[4], sh[4];           // byte offset of the lane's feature slot in a bin row; its byte's shift
-  unsigned vmask = 0u;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int kk = (k + rot) & 3;
-    const int fl = j * 4 + kk;
-    // low-cardinality features (srep > 1, NONA only): same-parity rows of a lane group collide on the few bins of
-    // such a feature (SQ_LDS_ADDR_CONFLICT ~ SQ_LDS_IDX_ACTIVE on HIGGS-like data with 3-valued b-tags); their
-    // updates go to copy (g >> 1) mod srep of the feature's bins, summed by the flush
-    const int c = (g >> 1) & (srep[fl] - 1);
-    offb[k] = (unsigned)fslot(fl) * 8u + ((unsigned)(c * snb[fl]) << 8);
-    sh[k] = 8u * kk;
-    if (wabs < W && wabs * 4 + kk < F) vmask |= 0xFFu << (8 * kk);
-  }
-  const bool live = vmask != 0u;     // a lane whose word is past the row adds nothing (no dummy atomics)
-  // FINE word: the 4 bytes are the 4 interleaved engine columns of ONE wide numeric feature (ops/binning.py), so
-  // their byte sum is the fine bin t = #{edges <= x} (NA: 4 x 255 = 1020) and one atomic into fine entry
-  // (bin t >> 2, column t & 3) replaces four; the flush rebuilds the four column histograms from the fine one
-  const bool fine = FINE && live && sfine[j * 4] != 0;
-  unsigned fsl[4];
-#pragma unroll
-  for (int l = 0; l < 4; ++l) fsl[l] = (unsigned)fslot(j * 4 + l) * 8u;
-  const int wc = min(wabs, W - 1);
-  const bool weighted = !UNIT && src.aw != nullptr;
-  char* Hb = (char*)h;
-  // entry (bin, slot) at byte (bin * FTILE + slot) * 8 = (bin << 8) + offb: one v_bfe_u32 + one v_lshl_add_u32
-  // per atomic (MEASURED: the shift / and / shift / add form the compiler made of the index expression was 4 VALU
-  // per atomic, and this loop is VALU-issue bound: ~12 VALU per LDS instruction in rocprofv3 PMC)
-  static_assert(FTILE * 8 == 256, "bin row of the LDS histogram is 256 bytes");
-  auto ent = [&](unsigned w, int k) -> unsigned long long* {
-    return (unsigned long long*)(Hb + ((__builtin_amdgcn_ubfe(w, sh[k], 8) << 8) + offb[k]));
-  };
-  for (int base = r0; base < r1; base += GR * UNR) {
-    unsigned wd[UNR];
-    float2 ab[UNR];
-    const bool whole = base + GR * UNR <= r1;          // block-uniform: no row of the batch is past r1
-    if (BUF && !FILT && whole) {
-      // consecutive rows: one voffset per batch, the unroll steps are SGPR offsets
-      const unsigned row0 = (unsigned)(base + g);
-      const unsigned vb = (row0 << src.lgw) + (unsigned)wc * 4u, va = row0 * 4u;
-#pragma unroll
-      for (int u = 0; u < UNR; ++u) {
-        wd[u] = __builtin_amdgcn_raw_buffer_load_b32(src.rb, vb, (unsigned)(u * GR) << src.lgw, 0);
-        const float y = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(src.ra, va, u * GR * 4, 0));
-        const float w = weighted ? __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(src.rw, va, u * GR * 4, 0))
-                                 : 1.f;
-        ab[u] = make_float2(w, y);
-      }
-    } else {
-      // unconditional loads (rows clamped into the node, words into the row): no exec-mask branches here;
-      // rows past r1 are skipped below, invalid words have vmask == 0
-#pragma unroll
-      for (int u = 0; u < UNR; ++u) {
-        const int idx = whole ? base + g + u * GR : min(base + g + u * GR, r1 - 1);
-        const int row = FILT ? lst[idx] : idx;
-        if (BUF) {
-          const unsigned ro = (unsigned)row;
-          wd[u] = __builtin_amdgcn_raw_buffer_load_b32(src.rb, (ro << src.lgw) + (unsigned)wc * 4u, 0, 0);
-          const float y = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(src.ra, ro * 4u, 0, 0));
-          const float w = weighted ? __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(src.rw, ro * 4u, 0, 0)) : 1.f;
-          ab[u] = make_float2(w, y);
-        } else {
-          // SoA aux planes: wY always, w only when rows are weighted (aw == null: unit weights)
-          ab[u] = make_float2(weighted ? src.aw[row] : 1.f, src.ay[row]);
-          wd[u] = src.bins32[(size_t)row * W + wc];
-        }
-      }
-    }
-    // One row word: every live lane adds all 4 of its word's features, valid or not: a feature past F (a partial last
-    // word) has the slot of a feature >= the tile's count, an LDS column the flush never reads, so its atomics are
-    // harmless — no divergent full / partial paths (the former per-row exec-mask juggling cost ~10 SALU per row).
-    // Only the rare NA-bin yy tally branches.
-    auto row = [&](int u) {
-      // UNIT (packed, every row weight exactly 1): constant count part, yy = wY^2 (no reciprocal)
-      if (lead) wyy += UNIT ? ab[u].y * ab[u].y : row_yy(ab[u].x, ab[u].y);
-      // (int) conversion truncates toward zero (v_cvt_i32_f32): the __float2int_rz form added a v_trunc_f32
-      const long long qa = UNIT ? (1ll << PACK_SHIFT) + (long long)(int)(ab[u].y * sp)
-                                : PACKED ? qpack(ab[u].x, ab[u].y, sp, sa, sb) : q64(ab[u].x, sa);
-      const long long qb = PACKED ? 0ll : q64(ab[u].y, sb);
-      const unsigned w = wd[u];
-      if (FINE && fine) {
-        const unsigned t = __builtin_amdgcn_sad_u8(w, 0u, 0u);          // sum of the 4 bytes
-        const unsigned l = t & 3u;
-        const unsigned so = (l & 2u) ? ((l & 1u) ? fsl[3] : fsl[2]) : ((l & 1u) ? fsl[1] : fsl[0]);
-        unsigned long long* p = (unsigned long long*)(Hb + (((t >> 2) << 8) + so));
-        atomicAdd(p, (unsigned long long)qa);
-        if (!PACKED) atomicAdd(p + HPLANE, (unsigned long long)qb);
-      } else if (live) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          unsigned long long* p = ent(w, k);
-          atomicAdd(p, (unsigned long long)qa);
-          if (!PACKED) atomicAdd(p + HPLANE, (unsigned long long)qb);
-        }
-      }
-      if (!NONA) {
-        const unsigned x = ~w | ~vmask;                   // a zero byte of x = an NA bin of a valid feature
-        if (((x - 0x01010101u) & ~x & 0x80808080u) != 0u) {
-          const float yy = UNIT ? ab[u].y * ab[u].y : row_yy(ab[u].x, ab[u].y);
-#pragma unroll
-          for (int k = 0; k < 4; ++k)
-            if (((vmask >> sh[k]) & 1u) && __builtin_amdgcn_ubfe(w, sh[k], 8) == NA_BIN)
-              atomicAdd(nayy + j * 4 + (sh[k] >> 3), yy);
-        }
-      }
-    };
-    if (whole) {
-#pragma unroll
-      for (int u = 0; u < UNR; ++u) row(u);
-    } else {
-#pragma unroll
-      for (int u = 0; u < UNR; ++u)
-        if (base + g + u * GR < r1) row(u);
-    }
-  }
-}
-
+// per feature (two atomics when not PACKED): entry (bin, slot) sits at byte (bin << 8) + offb, since a bin row of
+// the LDS histogram is FTILE * 8 = 256 bytes.
+// Low-cardinality features (srep > 1, NONA only): same-parity rows of a lane group collide on the few bins of such
+// a feature (SQ_LDS_ADDR_CONFLICT ~ SQ_LDS_IDX_ACTIVE on HIGGS-like data with 3-valued b-tags); their updates go to
+// copy (g >> 1) mod srep of the feature's bins, summed by the flush.
 // Plain (non-FILT) histogram of node rows [r0, r1) — one contiguous run of a node inside the block's tile range (a
 // whole window, not a tile): the per-lane setup runs once per run, and the loads of batch k + 1 are issued before the
 // atomics of batch k (double-buffered registers), so the wave's next rows are in flight while it feeds the LDS.
 // MEASURED (r5, scripts/mb_hist4.hip, 11M x 28): the pure LDS atomic rate is 8 cycles per ds_add_u64 wave-instruction
 // per CU (63 us for 308M updates) and the loads alone stream at ~6 TB/s (68 us); the per-tile loop with a per-row
-// fine / live branch reached only 135 us.
-template <bool PACKED, bool UNIT, bool NONA, bool BUF, bool FINE>
+// live branch reached only 135 us.
+template <bool PACKED, bool UNIT, bool NONA, bool BUF>
 __device__ __forceinline__ void hist_span(long long* h, float* nayy, const HistSrc& src, int W, int wabs, int F,
                                           bool lead, int r0, int r1, int g, int j, float& wyy, float sa, float sb,
-                                          float sp, const int* srep, const int* snb, const int* sfine,
-                                          bool no_atoms = false) {
+                                          float sp, const int* srep, const int* snb) {
   constexpr int GR = RPI, UNR = H2O_UNR;
   const int rot = g & 1;
   unsigned offb[4], sh[4];
@@ -611,11 +468,7 @@ __device__ __forceinline__ void hist_span(long long* h, float* nayy, const HistS
     sh[k] = 8u * kk;
     if (wabs < W && wabs * 4 + kk < F) vmask |= 0xFFu << (8 * kk);
   }
-  const bool live = vmask != 0u && !no_atoms;
-  const bool fine = FINE && live && sfine[j * 4] != 0;
-  unsigned fsl[4];
-#pragma unroll
-  for (int l = 0; l < 4; ++l) fsl[l] = (unsigned)fslot(j * 4 + l) * 8u;
+  const bool live = vmask != 0u;     // a lane whose word is past the row adds nothing (no dummy atomics)
   const int wc = min(wabs, W - 1);
   const bool weighted = !UNIT && src.aw != nullptr;
   char* Hb = (char*)h;
@@ -662,25 +515,15 @@ __device__ __forceinline__ void hist_span(long long* h, float* nayy, const HistS
                                 : PACKED ? qpack(ab[u].x, ab[u].y, sp, sa, sb) : q64(ab[u].x, sa);
       const long long qb = PACKED ? 0ll : q64(ab[u].y, sb);
       const unsigned w = wd[u];
-      if (FINE && fine) {
-        const unsigned t = __builtin_amdgcn_sad_u8(w, 0u, 0u);
-        const unsigned l = t & 3u;
-        const unsigned so = (l & 2u) ? ((l & 1u) ? fsl[3] : fsl[2]) : ((l & 1u) ? fsl[1] : fsl[0]);
-        unsigned long long* p = (unsigned long long*)(Hb + (((t >> 2) << 8) + so));
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        unsigned long long* p = (unsigned long long*)(Hb + ((__builtin_amdgcn_ubfe(w, sh[k], 8) << 8) + offb[k]));
         atomicAdd(p, (unsigned long long)qa);
         if (!PACKED) atomicAdd(p + HPLANE, (unsigned long long)qb);
-      } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          unsigned long long* p = (unsigned long long*)(Hb + ((__builtin_amdgcn_ubfe(w, sh[k], 8) << 8) + offb[k]));
-          atomicAdd(p, (unsigned long long)qa);
-          if (!PACKED) atomicAdd(p + HPLANE, (unsigned long long)qb);
-        }
       }
     };
     auto row = [&](int u) {
       if (lead) wyy += UNIT ? ab[u].y * ab[u].y : row_yy(ab[u].x, ab[u].y);
-      if (FINE && live) atoms(u);
       if (!NONA) {
         const unsigned w = wd[u];
         const unsigned x = ~w | ~vmask;
@@ -693,12 +536,12 @@ __device__ __forceinline__ void hist_span(long long* h, float* nayy, const HistS
         }
       }
     };
-    // !FINE: the lane's live test (a lane whose word holds no feature of the tile issues no atomics) is ONE exec-mask
+    // the lane's live test (a lane whose word holds no feature of the tile issues no atomics) is ONE exec-mask
     // branch around the batch's atomics, not one per row
     if (base + GR * UNR <= r1) {
 #pragma unroll
       for (int u = 0; u < UNR; ++u) row(u);
-      if (!FINE && live) {
+      if (live) {
 #pragma unroll
         for (int u = 0; u < UNR; ++u) atoms(u);
       }
@@ -706,7 +549,7 @@ __device__ __forceinline__ void hist_span(long long* h, float* nayy, const HistS
 #pragma unroll
       for (int u = 0; u < UNR; ++u)
         if (base + g + u * GR < r1) row(u);
-      if (!FINE && live) {
+      if (live) {
 #pragma unroll
         for (int u = 0; u < UNR; ++u)
           if (base + g + u * GR < r1) atoms(u);
@@ -723,12 +566,12 @@ struct FiltLane {   // per-lane setup of a FILT kernel (constant per block: feat
   unsigned offb[4];  // byte offset of the slot of byte k of the ROTATED word (see filt_atoms)
   unsigned vmask;    // valid features of the lane's word, in the original byte order
   int wc, rot;
-  bool live, fine, weighted, lead;
+  bool live, weighted, lead;
 };
 
-template <bool PACKED, bool UNIT, bool FINE>
+template <bool PACKED, bool UNIT>
 __device__ __forceinline__ FiltLane filt_lane(const HistSrc& src, int W, int wabs, int F, int g8, int j, bool lead,
-                                              const int* srep, const int* snb, const int* sfine) {
+                                              const int* srep, const int* snb) {
   FiltLane L;
   L.rot = g8 & 1;
   L.vmask = 0u;
@@ -741,7 +584,6 @@ __device__ __forceinline__ FiltLane filt_lane(const HistSrc& src, int W, int wab
     if (wabs < W && wabs * 4 + kk < F) L.vmask |= 0xFFu << (8 * kk);
   }
   L.live = L.vmask != 0u;
-  L.fine = FINE && L.live && sfine[j * 4] != 0;
   L.wc = min(wabs, W - 1);
   L.weighted = !UNIT && src.aw != nullptr;
   L.lead = lead;
@@ -771,7 +613,7 @@ __device__ __forceinline__ void filt_gather(const FiltLane& L, const HistSrc& sr
 // the atomics (and NA / yy tallies) of a gathered batch of n rows. The word is rotated by the lane group's parity
 // (byte k of the rotated word = feature 4j + ((k + rot) & 3), one v_alignbyte per row) so the byte extracts use
 // constant shifts; same-parity rows of a 16-lane group then add distinct features (bank-conflict-free layout).
-template <bool PACKED, bool UNIT, bool NONA, bool FINE>
+template <bool PACKED, bool UNIT, bool NONA>
 __device__ __forceinline__ void filt_atoms(const FiltLane& L, long long* h, float* nayy, int n, int g8, int j,
                                            const unsigned (&wd)[8], const float (&yv)[8], const float (&wv)[8],
                                            float& wyy, float sa, float sb, float sp) {
@@ -785,13 +627,7 @@ __device__ __forceinline__ void filt_atoms(const FiltLane& L, long long* h, floa
                               : PACKED ? qpack(x, yv[u], sp, sa, sb) : q64(x, sa);
     const long long qb = PACKED ? 0ll : q64(yv[u], sb);
     const unsigned w = wd[u];
-    if (FINE && L.fine) {
-      const unsigned t = __builtin_amdgcn_sad_u8(w, 0u, 0u);
-      const unsigned l = t & 3u;
-      unsigned long long* p = (unsigned long long*)(Hb + (((t >> 2) << 8) + (unsigned)fslot(j * 4 + (int)l) * 8u));
-      atomicAdd(p, (unsigned long long)qa);
-      if (!PACKED) atomicAdd(p + HPLANE, (unsigned long long)qb);
-    } else if (L.live) {
+    if (L.live) {
       const unsigned wr = __builtin_amdgcn_alignbyte(w, w, L.rot);
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
@@ -818,7 +654,7 @@ __device__ __forceinline__ void filt_atoms(const FiltLane& L, long long* h, floa
 // (deterministic, no global atomics). grid = (G, n_ftiles); each block takes a contiguous tile range.
 // FILT (odd levels): a node's tiles cover its PARENT's rows; only rows the parent's decision sends to
 // this child are accumulated, and ftile-0 blocks add the parent's left-going row count to nl_out.
-template <bool FILT, bool PACKED, bool UNIT, bool NONA, bool BUF, bool FINE>
+template <bool FILT, bool PACKED, bool UNIT, bool NONA, bool BUF>
 __global__ __launch_bounds__(BLK) void k_hist_build(
     const uint8_t* __restrict__ bins, int stride /*bytes per row, multiple of 4*/,
     const float* __restrict__ aw /*row weights or null (unit)*/, const float* __restrict__ ay /*w * Y*/,
@@ -827,9 +663,7 @@ __global__ __launch_bounds__(BLK) void k_hist_build(
     int slot_doubles, const double* __restrict__ qs /*[sa, sb, 1/sa, 1/sb, sp, 1/sp]*/,
     const Dec* __restrict__ pdec, int* __restrict__ nl_out, int f32, long long N, int planar, int lgw,
     const int* __restrict__ nbins_f /*[F] (NONA: low-cardinality spreading) or null*/,
-    const int* __restrict__ fine_f /*[F] 1 = column of an aligned 4-column wide numeric group, or null*/,
-    const uint8_t* __restrict__ fdir /*FILT: per row 0 = left / 1 = right of the parent split, or null*/,
-    int dbg /*A/B diagnostics (H2O_HIST_DBG): bit 0 skips the partial flush, bit 1 the plain pass's atomics*/) {
+    const uint8_t* __restrict__ fdir /*FILT: per row 0 = left / 1 = right of the parent split, or null*/) {
   constexpr bool packed = PACKED;
   extern __shared__ __attribute__((aligned(16))) long long smem64[];
   long long* h = smem64;                                 // 2 planes (PACKED: 1 -> two blocks per CU fit)
@@ -859,14 +693,12 @@ __global__ __launch_bounds__(BLK) void k_hist_build(
   const float sa = (float)qs[PACKED ? 10 : 0], sb = (float)qs[PACKED ? 12 : 1], sp = (float)qs[4];
   const HistSrc src = make_src(bins32, aw, ay, N, W, lgw);
   // per tile feature: bin count and copies of its bins (NONA: no NA bin, so copies of bins < nb never reach 255)
-  __shared__ int srep[FTILE], snb[FTILE], sfine[FTILE];
+  __shared__ int srep[FTILE], snb[FTILE];
   if (threadIdx.x < FTILE) {
     const int fg = ftile * FTILE + threadIdx.x;
-    const int fi = (fine_f && fg < F) ? fine_f[fg] : 0;
-    const int nb = (NONA && nbins_f && fg < F && !fi) ? nbins_f[fg] : 0;
+    const int nb = (NONA && nbins_f && fg < F) ? nbins_f[fg] : 0;
     srep[threadIdx.x] = (nb > 0 && nb * 4 <= NA_BIN) ? 4 : (nb > 0 && nb * 2 <= NA_BIN) ? 2 : 1;
     snb[threadIdx.x] = nb;
-    sfine[threadIdx.x] = fi;
   }
   __syncthreads();
 
@@ -881,8 +713,7 @@ __global__ __launch_bounds__(BLK) void k_hist_build(
   double wyy = 0.0;
   // FILT: histogram the wave's queued rows of the current node (before its LDS histogram is flushed)
   // FILT pipeline state: the batch gathered last (its atomics not yet issued)
-  const FiltLane FL = filt_lane<PACKED, UNIT, FINE>(src, W, wabs, Fl, lane >> 3, j, j == 0 && ftile == 0, srep, snb,
-                                                    sfine);
+  const FiltLane FL = filt_lane<PACKED, UNIT>(src, W, wabs, Fl, lane >> 3, j, j == 0 && ftile == 0, srep, snb);
   unsigned wdP[8];
   float yP[8], wP[8];
   int np = 0;                        // rows of the pending batch (0: none)
@@ -894,29 +725,28 @@ __global__ __launch_bounds__(BLK) void k_hist_build(
       float yN[8], wN[8];
       wave_sync_lds();
       filt_gather<UNIT, BUF>(FL, src, W, wq, qn, lane >> 3, wdN, yN, wN);
-      if (np > 0) filt_atoms<PACKED, UNIT, NONA, FINE>(FL, h, nayy, np, lane >> 3, j, wdP, yP, wP, wf2, sa, sb, sp);
-      filt_atoms<PACKED, UNIT, NONA, FINE>(FL, h, nayy, qn, lane >> 3, j, wdN, yN, wN, wf2, sa, sb, sp);
+      if (np > 0) filt_atoms<PACKED, UNIT, NONA>(FL, h, nayy, np, lane >> 3, j, wdP, yP, wP, wf2, sa, sb, sp);
+      filt_atoms<PACKED, UNIT, NONA>(FL, h, nayy, qn, lane >> 3, j, wdN, yN, wN, wf2, sa, sb, sp);
       qn = 0;
       wave_sync_lds();
     } else if (np > 0) {
-      filt_atoms<PACKED, UNIT, NONA, FINE>(FL, h, nayy, np, lane >> 3, j, wdP, yP, wP, wf2, sa, sb, sp);
+      filt_atoms<PACKED, UNIT, NONA>(FL, h, nayy, np, lane >> 3, j, wdP, yP, wP, wf2, sa, sb, sp);
     }
     np = 0;
     wyy += (double)wf2;
   };
   auto flush = [&]() {
     drain();
-    if (dbg & 1) return;
     double v[4] = {wyy, (double)lcnt, 0, 0};
     block_sum4(v, red);
     __syncthreads();
     const size_t so = (size_t)(blockIdx.x + cur) * slot_doubles;
     flush_partial(h, nayy, v[0], ftile, F, f32 ? (double*)((float*)partials + so) : partials + so, qs, packed, acc,
-                  f32 != 0, srep, snb, sfine);
+                  f32 != 0, srep, snb);
     if (FILT && threadIdx.x == 0 && v[1] != 0.0) atomicAdd(nl_out + cur_parent, (int)v[1]);
     __syncthreads();
   };
-  if (!FILT) {
+  if constexpr (!FILT) {
     // plain levels: the block's tiles are runs of whole node ranges — one hist_span per (node, packed window), no
     // per-tile node lookup or per-tile lane setup
     int t = t0;
@@ -944,35 +774,35 @@ __global__ __launch_bounds__(BLK) void k_hist_build(
         }
         const int we = packed ? min(re, rs + (PACK_MAX - since)) : re;
         float wf = 0.f;
-        hist_span<PACKED, UNIT, NONA, BUF, FINE>(h, nayy, src, W, wabs, Fl, j == 0 && ftile == 0, rs, we, g, j, wf, sa,
-                                                 sb, sp, srep, snb, sfine, (dbg & 2) != 0);
+        hist_span<PACKED, UNIT, NONA, BUF>(h, nayy, src, W, wabs, Fl, j == 0 && ftile == 0, rs, we, g, j, wf, sa, sb,
+                                           sp, srep, snb);
         wyy += (double)wf;
         since += we - rs;
         rs = we;
       }
     }
-  }
-  for (int t = FILT ? t0 : t1; t < t1; ++t) {
-    const int node = find_node(tile_prefix, n_nodes, t);
-    const Node nd = nodes[node];
-    if (!nd.build) continue;
-    const int r0 = nd.start + (t - tile_prefix[node]) * TILE;
-    const int r1 = min(r0 + TILE, nd.start + nd.len);
-    // new node, or (packed) the flush window is full: flush the LDS tile and restart it
-    if (node != cur || (packed && since + (r1 - r0) > PACK_MAX)) {
-      if (cur >= 0) flush();
-      acc = node == cur;    // same node, next window: add into the partial stored by the first flush
-      lds_zero64(h, packed ? HPLANE : 2 * HPLANE);
-      for (int i = threadIdx.x; i < FTILE; i += blockDim.x) nayy[i] = 0.f;
-      if (FILT && threadIdx.x < (int)(sizeof(Dec) / 4))
-        ((int*)&spd)[threadIdx.x] = ((const int*)(pdec + nd.parent))[threadIdx.x];
-      wyy = 0.0;
-      lcnt = 0;
-      since = 0;
-      cur = node;
-      cur_parent = nd.parent;
-      __syncthreads();
-      if (FILT) {
+  } else {
+    // filtered (odd) levels: tile by tile over the PARENT's rows
+    for (int t = t0; t < t1; ++t) {
+      const int node = find_node(tile_prefix, n_nodes, t);
+      const Node nd = nodes[node];
+      if (!nd.build) continue;
+      const int r0 = nd.start + (t - tile_prefix[node]) * TILE;
+      const int r1 = min(r0 + TILE, nd.start + nd.len);
+      // new node, or (packed) the flush window is full: flush the LDS tile and restart it
+      if (node != cur || (packed && since + (r1 - r0) > PACK_MAX)) {
+        if (cur >= 0) flush();
+        acc = node == cur;    // same node, next window: add into the partial stored by the first flush
+        lds_zero64(h, packed ? HPLANE : 2 * HPLANE);
+        for (int i = threadIdx.x; i < FTILE; i += blockDim.x) nayy[i] = 0.f;
+        if (threadIdx.x < (int)(sizeof(Dec) / 4))
+          ((int*)&spd)[threadIdx.x] = ((const int*)(pdec + nd.parent))[threadIdx.x];
+        wyy = 0.0;
+        lcnt = 0;
+        since = 0;
+        cur = node;
+        cur_parent = nd.parent;
+        __syncthreads();
         flt.feat = spd.feat;
         flt.fptr = bins + bin_off(0, spd.feat, stride, N, planar);
         flt.fstride = planar ? 32 : stride;
@@ -984,10 +814,8 @@ __global__ __launch_bounds__(BLK) void k_hist_build(
         if (fdir) { flt.bin = 1; flt.na_left = 0; flt.is_cat = 0; }    // direction bytes: 0 goes left
         flt.count = ftile == 0;
       }
-    }
-    since += r1 - r0;
-    float wf = 0.f;
-    if (FILT) {
+      since += r1 - r0;
+      float wf = 0.f;
       // the split bytes of this tile were prefetched during the previous tile's atomics when both tiles
       // belong to the same node (the common case); a node change loads them here
       // split bytes are prefetched TWO tiles ahead (same node: same filter): the direction loads are this pass's HBM
@@ -1028,13 +856,13 @@ __global__ __launch_bounds__(BLK) void k_hist_build(
         if (lane < rest) wq[lane] = v0;
         if (lane + 64 < rest) wq[64 + lane] = v1;
         qn = rest;
-        if (np > 0) filt_atoms<PACKED, UNIT, NONA, FINE>(FL, h, nayy, np, lane >> 3, j, wdP, yP, wP, wf, sa, sb, sp);
+        if (np > 0) filt_atoms<PACKED, UNIT, NONA>(FL, h, nayy, np, lane >> 3, j, wdP, yP, wP, wf, sa, sb, sp);
 #pragma unroll
         for (int u = 0; u < 8; ++u) { wdP[u] = wdN[u]; yP[u] = yN[u]; wP[u] = wN[u]; }
         np = 64;
       }
+      wyy += (double)wf;
     }
-    wyy += (double)wf;
   }
   if (cur >= 0) flush();
 }
@@ -1354,8 +1182,9 @@ __device__ void split_find_group(const HistRead& hv, int node, int f, int gg, in
 }
 
 // k_split_find: best split point per (node, feature). grid = (C, F), block 256 (thread = bin).
+// GRP: the run has wide-categorical groups (SplitParams.gcat); without them the group search is not compiled in.
 template <bool GRP>
-__device__ __forceinline__ void split_find_body(
+__global__ __launch_bounds__(256) void k_split_find(
     double* __restrict__ hist, int slot_doubles, const int* __restrict__ meta, int F,
     const int* __restrict__ nbins_f, const int* __restrict__ iscat_f, const int* __restrict__ mono_f,
     SplitParams p, int level, Cand* __restrict__ cand, double* __restrict__ root_w,
@@ -1858,7 +1687,6 @@ struct PlanReduce {          // k_plan's fused k_split_reduce (cand == null: dec
   const unsigned char* node_ok;
   const int* fgroup;
   int cfs, ccap;             // rank-major sliced candidates (see cand_at); 0 = [cap][F]
-  int no_wave;               // 1: levels of <= 64 nodes take the block plan too (H2O_PLAN_WAVE=0)
 };
 #define PLAN_REDUCE_MAX 256
 
@@ -1925,11 +1753,12 @@ __device__ void level_tile_prefix(const Node* __restrict__ next, int nn, int* __
 // Odd depth (next level even): the children's ranges are only known after k_route, which fills each
 //   odd node's region of the next buffer from both ends; this kernel sets up those cursors
 //   (curs[c] = {front, back, region start, region end}, from the parent's left count prev_nl) and
+//   k_route's last block turns the final cursors into ranges + tile prefix.
+// Levels of at most 64 nodes are planned by one wave (plan_wave), larger ones by the whole block.
+
 // the fields of a decision the plan reads (the 176-B record carries a 1024-bit set it never needs)
 struct DecLite { int feat; double wl, wr; };
 __device__ __forceinline__ DecLite dec_lite(const Dec* d) { return DecLite{d->feat, d->wl, d->wr}; }
-
-//   k_ranges turns the final cursors into ranges + tile prefix.
 
 __device__ __forceinline__ int wave_excl_scan(int v, int* total) {
   const int lane = threadIdx.x & 63;
@@ -2021,13 +1850,13 @@ __device__ void plan_wave(
   }
 }
 
-__device__ void plan_body(
+// (the k_plan note is above DecLite; pr.cand != null: the block first picks the level's decisions, reduce_node)
+__global__ __launch_bounds__(1024) void k_plan(
     const Node* __restrict__ nodes, const int* __restrict__ meta, Dec* __restrict__ dec,
     int* __restrict__ node_nl, const int* __restrict__ prev_nl, int4* __restrict__ curs,
     int* __restrict__ child_l, int* __restrict__ child_r,
     Node* __restrict__ next, int* __restrict__ next_tile_prefix, int* __restrict__ next_meta,
-    int* __restrict__ next_build_prefix,
-    int* __restrict__ counters, int* __restrict__ scratch /* >= cap_cur ints */,
+    int* __restrict__ next_build_prefix, int* __restrict__ counters, int* __restrict__ scratch /* >= cap_cur ints */,
     int depth, int max_depth, double min_w, int cap_next, int leaf_cap, PlanReduce pr) {
   __shared__ int sh[17];
   const int n = meta[0];
@@ -2038,7 +1867,7 @@ __device__ void plan_body(
                   pr.cfs, pr.ccap);
     __syncthreads();                     // the block's own decisions (global) before the plan reads them
   }
-  if (n <= 64 && !pr.no_wave) {       // small level: wave 0 alone (the other waves are done)
+  if (n <= 64) {                       // small level: wave 0 alone (the other waves are done)
     if (tid < 64)
       plan_wave(nodes, n, dec, node_nl, prev_nl, curs, child_l, child_r, next, next_tile_prefix, next_meta,
                 next_build_prefix, counters, depth, max_depth, min_w, cap_next, leaf_cap);
@@ -2114,7 +1943,7 @@ __device__ void plan_body(
     if (ra) { if (flags & 2) ri = ao; ++ao; }
     child_l[i] = (li >= 0) ? li : -1 - min(lo++, leaf_cap - 1);
     child_r[i] = (ri >= 0) ? ri : -1 - min(lo++, leaf_cap - 1);
-    // children of an even node inherit its range (odd level); children of an odd node get theirs in k_ranges
+    // children of an even node inherit its range (odd level); children of an odd node get theirs from k_route
     if (li >= 0 && ri >= 0) {
       const bool build_left = d.wl <= d.wr;  // global weights: identical choice on every rank
       next[li] = Node{nd.start, nd.len, build_left ? 1 : 0, i, ri, 0, 0, 0};
@@ -2138,74 +1967,6 @@ __device__ void plan_body(
   }
 }
 
-__global__ __launch_bounds__(1024) void k_plan(
-    const Node* __restrict__ nodes, const int* __restrict__ meta, Dec* __restrict__ dec,
-    int* __restrict__ node_nl, const int* __restrict__ prev_nl, int4* __restrict__ curs,
-    int* __restrict__ child_l, int* __restrict__ child_r,
-    Node* __restrict__ next, int* __restrict__ next_tile_prefix, int* __restrict__ next_meta,
-    int* __restrict__ next_build_prefix, int* __restrict__ counters, int* __restrict__ scratch,
-    int depth, int max_depth, double min_w, int cap_next, int leaf_cap, PlanReduce pr) {
-  plan_body(nodes, meta, dec, node_nl, prev_nl, curs, child_l, child_r, next, next_tile_prefix, next_meta,
-            next_build_prefix, counters, scratch, depth, max_depth, min_w, cap_next, leaf_cap, pr);
-}
-
-template <bool GRP>
-__global__ __launch_bounds__(256) void k_split_find(
-    double* __restrict__ hist, int slot_doubles, const int* __restrict__ meta, int F,
-    const int* __restrict__ nbins_f, const int* __restrict__ iscat_f, const int* __restrict__ mono_f,
-    SplitParams p, int level, Cand* __restrict__ cand, double* __restrict__ root_w,
-    const float* __restrict__ edges, int adapt_nb, int f0, int FL, Derive dv) {
-  split_find_body<GRP>(hist, slot_doubles, meta, F, nbins_f, iscat_f, mono_f, p, level, cand, root_w, edges, adapt_nb,
-                       f0, FL, dv);
-}
-
-// k_split_find with the level's k_plan folded into its LAST block (single process, <= PLAN_REDUCE_MAX nodes): every
-// (node, feature) block publishes its candidate with an agent-scope RELEASE ticket on `done`; the block drawing the
-// final ticket acquires (L2 invalidate) and runs the plan — reduce_node over the candidates, child numbering, the
-// next level's node list and tile prefixes — with its 256 threads. One launch per level instead of two.
-struct PlanArgs {
-  const Node* nodes;
-  const int* meta;
-  Dec* dec;
-  int* node_nl;
-  const int* prev_nl;
-  int4* curs;
-  int* child_l;
-  int* child_r;
-  Node* next;
-  int* next_tp;
-  int* next_meta;
-  int* next_bp;
-  int* counters;
-  int* scratch;
-  int depth, max_depth, cap_next, leaf_cap;
-  double min_w;
-  PlanReduce pr;
-  int* done;       // zero before the launch; the last block resets it
-};
-
-__global__ __launch_bounds__(256) void k_split_find_plan(
-    double* __restrict__ hist, int slot_doubles, const int* __restrict__ meta, int F,
-    const int* __restrict__ nbins_f, const int* __restrict__ iscat_f, const int* __restrict__ mono_f,
-    SplitParams p, int level, Cand* __restrict__ cand, double* __restrict__ root_w,
-    const float* __restrict__ edges, int adapt_nb, int f0, int FL, Derive dv, PlanArgs pa) {
-  split_find_body<false>(hist, slot_doubles, meta, F, nbins_f, iscat_f, mono_f, p, level, cand, root_w, edges,
-                         adapt_nb, f0, FL, dv);
-  __shared__ int s_last;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const int total = (int)(gridDim.x * gridDim.y);
-    s_last = __hip_atomic_fetch_add(pa.done, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT) == total - 1;
-  }
-  __syncthreads();
-  if (!s_last) return;
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  plan_body(pa.nodes, pa.meta, pa.dec, pa.node_nl, pa.prev_nl, pa.curs, pa.child_l, pa.child_r, pa.next, pa.next_tp,
-            pa.next_meta, pa.next_bp, pa.counters, pa.scratch, pa.depth, pa.max_depth, pa.min_w, pa.cap_next,
-            pa.leaf_cap, pa.pr);
-  if (threadIdx.x == 0) __hip_atomic_store(pa.done, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 // Interaction constraints (GlobalInteractionConstraints / BranchInteractionConstraints): a child may split
 // on the features its parent allowed AND that interact with the parent's split feature:
 // ok[child][f] = ok[parent][f] & map[parent split feature][f]. grid = next-level capacity, block 64.
@@ -2219,32 +1980,6 @@ __global__ __launch_bounds__(64) void k_ic_next(const Node* __restrict__ next, c
   const int sf = dec[par].feat;
   for (int f = threadIdx.x; f < F; f += 64)
     ok_next[(size_t)c * F + f] = (sf >= 0 && ok_cur[(size_t)par * F + f] && ic_map[(size_t)sf * F + f]) ? 1 : 0;
-}
-
-// k_ranges: after k_route filled the odd level's regions, give each even-level node its range
-// (left child: [region start, front); right child: [back, region end)) and build the tile prefix.
-__global__ __launch_bounds__(1024) void k_ranges(Node* __restrict__ next, const int4* __restrict__ curs,
-                                                 int* __restrict__ tp, int* __restrict__ bp, int* __restrict__ meta) {
-  __shared__ int sh[17];
-  const int nn = meta[0];
-  for (int i = threadIdx.x; i < nn; i += blockDim.x) {
-    Node nd = next[i];
-    const int4 c = curs[nd.parent];
-    if (nd.dir == 0) { nd.start = c.z; nd.len = c.x - c.z; }
-    else { nd.start = c.y; nd.len = c.w - c.y; }
-    next[i] = nd;
-  }
-  __syncthreads();
-  level_tile_prefix(next, nn, tp, bp, meta, sh);
-}
-
-// k_zero_hist: zero the compact build slots (slot = parent) of next-level nodes built directly.
-__global__ void k_zero_hist(double* __restrict__ hbuild, const Node* __restrict__ next,
-                            const int* __restrict__ meta, int slot_doubles) {
-  const int node = blockIdx.y;
-  if (node >= meta[0] || !next[node].build) return;
-  double* s = hbuild + (size_t)next[node].parent * slot_doubles;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < slot_doubles; i += gridDim.x * blockDim.x) s[i] = 0.0;
 }
 
 // k_hist_pack: feature-sliced reduce-scatter staging. Node slots [n][slot] (bin-major (bin, f) pairs, then
@@ -2491,11 +2226,13 @@ __device__ __forceinline__ void route_tile(
   }
 }
 
-// k_ranges work folded into the route's LAST block (ro.done != null): every block counts itself out on ro.done
+// The route's LAST block gives each node of level e + 2 its range (left child: [region start, front); right child:
+// [back, region end)) and builds the level's tile prefix: every block counts itself out on ro.done
 // after its cursor atomics have returned (it used their results), so the block that draws the final ticket sees the
 // final cursors. The cursors are read back with agent-scope atomic loads (they were only ever updated by atomics at
 // the coherence point; no fence / L2 write-back is needed), the node list and prefixes are written with plain
-// stores that the next kernel reads. Saves one launch per route (MEASURED r5: k_ranges 4.6 us, 2 per tree).
+// stores that the next kernel reads. (MEASURED r5: the separate one-block kernel this replaced took 4.6 us, 2 per
+// tree.)
 struct RangesOut {
   Node* next;
   int* tp;
@@ -2575,7 +2312,7 @@ __global__ __launch_bounds__(256) void k_row_dir(const uint8_t* __restrict__ bin
 struct LevelPtrs { const Dec* dec; const int* cl; const int* cr; long long cap; };
 
 template <int NV, bool GRP>
-__device__ __forceinline__ void leaf_assign_body(
+__global__ __launch_bounds__(256) void k_leaf_assign(
     const uint8_t* __restrict__ bins, int stride, long long N, const LevelPtrs* __restrict__ lv, int D,
     const float* __restrict__ an, const float* __restrict__ ad, const double* __restrict__ qs,
     int* __restrict__ leaf_of_row, unsigned long long* __restrict__ leafq, int leaf_cap, int n_nodes, int planar,
@@ -2718,29 +2455,6 @@ __global__ void k_leafsum_finish(unsigned long long* __restrict__ leafq, const d
                                  double* __restrict__ leafsum, LeafVals lv) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) leafsum_one(leafq, qs, n, leafsum, lv, i);
-}
-
-// k_leaf_assign with k_leafsum_finish folded into its LAST block: every block's leaf-sum atomics are ordered before
-// its agent-scope RELEASE ticket on `done`; the block drawing the final ticket acquires and finishes all leaf_cap
-// leaves (fp64 sums, re-zeroed fixed-point slots, closed-form values). One launch per tree instead of two.
-// (FUSE is a template switch: the tail costs the unfused kernel 14 VGPRs — 34 -> 48 — and MEASURED r5 115 -> 140 us)
-template <int NV, bool FUSE, bool GRP>
-__global__ __launch_bounds__(256) void k_leaf_assign(
-    const uint8_t* __restrict__ bins, int stride, long long N, const LevelPtrs* __restrict__ lv, int D,
-    const float* __restrict__ an, const float* __restrict__ ad, const double* __restrict__ qs,
-    int* __restrict__ leaf_of_row, unsigned long long* __restrict__ leafq, int leaf_cap, int n_nodes, int planar,
-    const uint8_t* __restrict__ lvl2, double* __restrict__ leafsum, LeafVals vals, int* __restrict__ done) {
-  leaf_assign_body<NV, GRP>(bins, stride, N, lv, D, an, ad, qs, leaf_of_row, leafq, leaf_cap, n_nodes, planar, lvl2);
-  if (!FUSE || !done) return;
-  __shared__ int s_last;
-  __syncthreads();
-  if (threadIdx.x == 0)
-    s_last = __hip_atomic_fetch_add(done, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT) == (int)gridDim.x - 1;
-  __syncthreads();
-  if (!s_last) return;
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  for (int i = threadIdx.x; i < leaf_cap; i += blockDim.x) leafsum_one(leafq, qs, leaf_cap, leafsum, vals, i);
-  if (threadIdx.x == 0) __hip_atomic_store(done, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3071,34 +2785,20 @@ __global__ __launch_bounds__(256) void k_fine16_build(const uint8_t* __restrict_
 }
 
 // ================================================================================================
-// C ABI launchers (called through ctypes with raw device pointers and the current HIP stream).
-static int hist_dbg() {   // H2O_HIST_DBG: diagnostics of the histogram pass (A/B timing only; never in a real run)
-  const char* e = getenv("H2O_HIST_DBG");
-  return e ? atoi(e) : 0;
-}
-
-template <bool FILT, bool PACKED, bool UNIT, bool NONA, bool BUF>
-static void launch_hist4(dim3 grid, size_t lds, hipStream_t s, const void* bins, int stride, const void* aw,
-                         const void* ay, const void* nodes, const void* tile_prefix, const void* meta, int F,
-                         void* partials, int slot_doubles, const void* qs, const void* pdec, void* nl_out, int f32,
-                         long long N, int planar, int lgw, const void* nbins_f, const void* fine_f, const void* fdir) {
-#define H2O_HB(FINE_)                                                                                              \
-  hipLaunchKernelGGL((k_hist_build<FILT, PACKED, UNIT, NONA, BUF, FINE_>), grid, dim3(BLK), lds, s,               \
-                     (const uint8_t*)bins, stride, (const float*)aw, (const float*)ay, (const Node*)nodes,         \
-                     (const int*)tile_prefix, (const int*)meta, F, (double*)partials, slot_doubles, (const double*)qs, \
-                     (const Dec*)pdec, (int*)nl_out, f32, N, planar, lgw, (const int*)nbins_f, (const int*)fine_f,  \
-                     (const uint8_t*)fdir, hist_dbg())
-  // FINE (fine-bin atomics of aligned 4-column wide groups, off by default): a separate instantiation, so the common
-  // kernels carry no per-row fine / live branch
-  if (fine_f) H2O_HB(true); else H2O_HB(false);
-#undef H2O_HB
+// Host launchers. Only the `extern "C"` functions are exported (called through ctypes with raw device pointers and
+// the current HIP stream); the per-kernel launchers are internal to the native tree plan further down.
+// H2O_HIST_BUF=0: 64-bit addressing in k_hist_build. Read at every launch, not cached like the other switches:
+// tests/test_tree_engine.py and scripts/hist_ab.py flip it inside one process to reach both sets of kernels.
+static bool hist_buf_off() {
+  const char* e = getenv("H2O_HIST_BUF");
+  return e && strcmp(e, "0") == 0;
 }
 
 template <bool PACKED, bool UNIT>
 static void launch_hist(dim3 grid, size_t lds, hipStream_t s, const void* bins, int stride, const void* aw,
                         const void* ay, const void* nodes, const void* tile_prefix, const void* meta, int F,
                         void* partials, int slot_doubles, const void* qs, const void* pdec, void* nl_out, int f32,
-                        long long N, int planar, const void* nbins_f, const void* fine_f, const void* fdir) {
+                        long long N, int planar, const void* nbins_f, const void* fdir) {
   // flags: bit 0 planar bins, bit 1 no NA bin anywhere (NONA kernels)
   const bool nona = (planar >> 1) & 1;
   planar &= 1;
@@ -3109,12 +2809,12 @@ static void launch_hist(dim3 grid, size_t lds, hipStream_t s, const void* bins, 
   int lgw = -1;
   for (int k = 0; k < 12; ++k) if (rowb == (1 << k)) lgw = k;
   // (buffer offsets and NUM_RECORDS are unsigned 32-bit: up to 4 GiB per buffer, e.g. a 100M-row 32-byte plane)
-  const char* e_buf = getenv("H2O_HIST_BUF");     // A/B and test switch: 0 = 64-bit addressing
-  const bool buf = lgw >= 0 && bytes < (1ull << 32) && (unsigned long long)N * 4ull < (1ull << 32) &&
-                   !(e_buf && strcmp(e_buf, "0") == 0);
-#define H2O_HIST_CASE(F_, N_, B_) \
-  launch_hist4<F_, PACKED, UNIT, N_, B_>(grid, lds, s, bins, stride, aw, ay, nodes, tile_prefix, meta, F, partials, \
-                                          slot_doubles, qs, pdec, nl_out, f32, N, planar, lgw, nbins_f, fine_f, fdir)
+  const bool buf = lgw >= 0 && bytes < (1ull << 32) && (unsigned long long)N * 4ull < (1ull << 32) && !hist_buf_off();
+#define H2O_HIST_CASE(F_, N_, B_)                                                                                \
+  hipLaunchKernelGGL((k_hist_build<F_, PACKED, UNIT, N_, B_>), grid, dim3(BLK), lds, s, (const uint8_t*)bins,    \
+                     stride, (const float*)aw, (const float*)ay, (const Node*)nodes, (const int*)tile_prefix,    \
+                     (const int*)meta, F, (double*)partials, slot_doubles, (const double*)qs, (const Dec*)pdec,  \
+                     (int*)nl_out, f32, N, planar, lgw, (const int*)nbins_f, (const uint8_t*)fdir)
   const bool filt = pdec != nullptr;
   if (filt) {
     if (nona) { if (buf) H2O_HIST_CASE(true, true, true); else H2O_HIST_CASE(true, true, false); }
@@ -3134,7 +2834,7 @@ static void reduce_launch(const void* partials, int slot_doubles, int used, cons
   if (lo_F >= F) lo_F = 0;
   const int n = lo_F > 0 ? NBIN * 2 * lo_F + F + 1 : used;
   // many node slots at this level (>= 16: a built node's rows span <= ~1/8 of the grid): column-wave form
-  if (cap >= 16 && !getenv("H2O_REDUCE_SPLIT")) {
+  if (cap >= 16) {
     const int gx = (n + 64 * RW - 1) / (64 * RW);
     hipLaunchKernelGGL((k_hist_reduce<P, TO, true>), dim3(gx, cap), dim3(RW * 64), 0, s, (const P*)partials,
                        slot_doubles, used, (const Node*)nodes, (const int*)bp, (const int*)meta, grid, (TO*)out,
@@ -3147,11 +2847,9 @@ static void reduce_launch(const void* partials, int slot_doubles, int used, cons
                      (double*)hist_next, (const double*)hist_cur, lo_F);
 }
 
-extern "C" {
+extern "C" int h2o_abi_version() { return H2O_ABI_VERSION; }
 
-int h2o_abi_version() { return H2O_ABI_VERSION; }
-
-int h2o_tree_sizes(int* out) {
+extern "C" int h2o_tree_sizes(int* out) {
   out[7] = AMAX_SHARDS;
   out[8] = LEAFQ_STRIPES;
   out[0] = sizeof(Node); out[1] = sizeof(Dec); out[2] = sizeof(Cand); out[3] = TILE; out[4] = FTILE;
@@ -3161,36 +2859,32 @@ int h2o_tree_sizes(int* out) {
 }
 
 // partials: >= (grid + max nodes of the level) slots of slot_doubles. nbins_f (nullable): per-feature bin counts,
-// which let NONA launches spread the updates of low-cardinality features over copies of their bins. fine_f
-// (nullable): 1 for the columns of word-aligned 4-column wide numeric groups (one fine atomic per row and group).
+// which let NONA launches spread the updates of low-cardinality features over copies of their bins.
 // nft_lim > 0: only the first nft_lim feature tiles (planes) are built (narrow levels; the slot layout stays F)
-int h2o_hist_build(const void* bins, int stride, const void* aw, const void* ay, const void* nodes,
-                   const void* tile_prefix, const void* meta, int F, void* partials, int slot_doubles, const void* qs,
-                   int grid, int packed, const void* pdec, void* nl_out, int f32, long long N, int planar,
-                   const void* nbins_f, const void* fine_f, int nft_lim, const void* fdir, hipStream_t s) {
+static int h2o_hist_build(const void* bins, int stride, const void* aw, const void* ay, const void* nodes,
+                          const void* tile_prefix, const void* meta, int F, void* partials, int slot_doubles,
+                          const void* qs, int grid, int packed, const void* pdec, void* nl_out, int f32, long long N,
+                          int planar, const void* nbins_f, int nft_lim, const void* fdir, hipStream_t s) {
   int nft = (F + FTILE - 1) / FTILE;
   if (nft_lim > 0 && nft_lim < nft) nft = nft_lim;
-  // A/B switches: H2O_HIST_REPL=0 drops the low-cardinality bin replicas, H2O_HIST_FINE=1 enables the
-  // fine-bin atomics of 4-column wide groups (MEASURED slower: AUTO 11M plain pass 482 vs 325 us, r4)
-  const char* e_repl = getenv("H2O_HIST_REPL");
-  const char* e_fine = getenv("H2O_HIST_FINE");
-  const bool repl = !e_repl || strcmp(e_repl, "0") != 0;
-  const bool fine = e_fine && strcmp(e_fine, "1") == 0;
-  if (!repl) nbins_f = nullptr;
-  if (!fine) fine_f = nullptr;
   // packed mode needs one int64 plane (66 KB): two 16-wave blocks share a CU (32 waves, 8 per SIMD)
   const size_t lds = (packed ? HIST_LDS_BYTES - HPLANE * 8 : HIST_LDS_BYTES) + HIST_LDS_TAIL;
   const dim3 gr(grid, nft);
   if (packed && aw == nullptr)   // unit row weights (the trainer dropped the w plane)
-    launch_hist<true, true>(gr, lds, s, bins, stride, aw, ay, nodes, tile_prefix, meta, F, partials, slot_doubles, qs, pdec, nl_out, f32, N, planar, nbins_f, fine_f, fdir);
-  else if (packed) launch_hist<true, false>(gr, lds, s, bins, stride, aw, ay, nodes, tile_prefix, meta, F, partials, slot_doubles, qs, pdec, nl_out, f32, N, planar, nbins_f, fine_f, fdir);
-  else launch_hist<false, false>(gr, lds, s, bins, stride, aw, ay, nodes, tile_prefix, meta, F, partials, slot_doubles, qs, pdec, nl_out, f32, N, planar, nbins_f, fine_f, fdir);
+    launch_hist<true, true>(gr, lds, s, bins, stride, aw, ay, nodes, tile_prefix, meta, F, partials, slot_doubles, qs,
+                            pdec, nl_out, f32, N, planar, nbins_f, fdir);
+  else if (packed)
+    launch_hist<true, false>(gr, lds, s, bins, stride, aw, ay, nodes, tile_prefix, meta, F, partials, slot_doubles, qs,
+                             pdec, nl_out, f32, N, planar, nbins_f, fdir);
+  else
+    launch_hist<false, false>(gr, lds, s, bins, stride, aw, ay, nodes, tile_prefix, meta, F, partials, slot_doubles, qs,
+                              pdec, nl_out, f32, N, planar, nbins_f, fdir);
   return (int)hipGetLastError();
 }
 
 
 // fine: [ceil(nslot / 16)][N][16] uint16 (see k_fine16_build); nslot <= 64
-int h2o_fine16_build(const void* master, int planes, long long N, const void* cslot, int nslot, void* fine,
+extern "C" int h2o_fine16_build(const void* master, int planes, long long N, const void* cslot, int nslot, void* fine,
                      hipStream_t s) {
   if (nslot < 1 || nslot > 64 || planes < 1 || N <= 0) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(k_fine16_build, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, (const uint8_t*)master, planes,
@@ -3199,7 +2893,7 @@ int h2o_fine16_build(const void* master, int planes, long long N, const void* cs
 }
 
 // Root histogram from the 16-bit fine planes (k_hist_root16): packed modes only (packed 1 / 2); planes = slots / 16.
-int h2o_hist_root16(const void* fine, int planes, const void* aw, const void* ay, long long N, const void* meta,
+static int h2o_hist_root16(const void* fine, int planes, const void* aw, const void* ay, long long N, const void* meta,
                     const void* fcol, const void* fnc, int F, void* partials, int slot_doubles, const void* qs, int grid,
                     int f32, hipStream_t s) {
   if (planes < 1 || grid < 1 || N <= 0) return (int)hipErrorInvalidValue;
@@ -3218,7 +2912,7 @@ int h2o_hist_root16(const void* fine, int planes, const void* aw, const void* ay
 // grid: the G the matching h2o_hist_build ran with; out / hist_next may be null (see k_hist_reduce).
 // out: compact build slots of ostride values (0: slot_doubles), fp32 when out_f32 (the exchange's wire dtype)
 // lo_F > 0 (narrow level): only the entries of columns < lo_F (and the NA / node tails) are summed
-int h2o_hist_reduce(const void* partials, int slot_doubles, int used, const void* nodes, const void* bp,
+static int h2o_hist_reduce(const void* partials, int slot_doubles, int used, const void* nodes, const void* bp,
                     const void* meta, int cap, int grid, void* out, void* hist_next, const void* hist_cur,
                     int f32, int out_f32, int ostride, int lo_F, hipStream_t s) {
   if (ostride <= 0) ostride = slot_doubles;
@@ -3233,7 +2927,7 @@ int h2o_hist_reduce(const void* partials, int slot_doubles, int used, const void
   return (int)hipGetLastError();
 }
 
-int h2o_leaf_values(const void* leafsum, int n, int log_link, double scale, double kclamp, double mx, double lam,
+static int h2o_leaf_values(const void* leafsum, int n, int log_link, double scale, double kclamp, double mx, double lam,
                     double l1, void* out,
                     hipStream_t s) {
   hipLaunchKernelGGL(k_leaf_values, dim3((n + 255) / 256), dim3(256), 0, s, (const double*)leafsum, n, log_link,
@@ -3257,20 +2951,7 @@ static int split_find_launch(void* hist, int slot_doubles, const void* meta, int
   return (int)hipGetLastError();
 }
 
-int h2o_split_find(const void* hist, int slot_doubles, const void* meta, int cap, int F, const void* nbins_f,
-                   const void* iscat_f, const void* mono_f, double min_w, double msi, double lambda_, double alpha,
-                   double gamma, int mode, int random_split, unsigned long long seed, int level, void* cand,
-                   void* root_w, const void* edges, int adapt_nb, int hist_type, int f0, int FL, hipStream_t s) {
-  SplitParams p;
-  p.min_w = min_w; p.min_split_improvement = msi; p.lambda = lambda_; p.alpha = alpha; p.gamma = gamma;
-  p.mode = mode; p.random_split = random_split; p.seed = seed; p.hist_type = hist_type; p.fcut = 0;
-  p.vrange = nullptr; p.hprev = nullptr; p.pdec = nullptr; p.rnodes = nullptr; p.fgroup = nullptr; p.edges_all = nullptr;
-  p.range_on = 0; p.pad_r = 0; p.gcat = nullptr; p.rootw = nullptr;
-  return split_find_launch((void*)hist, slot_doubles, meta, cap, F, nbins_f, iscat_f, mono_f, p, level, cand, root_w,
-                           edges, adapt_nb, f0, FL, Derive{nullptr, 0, 0, nullptr, nullptr}, s);
-}
-
-int h2o_split_reduce(const void* cand, const void* meta, int cap, int F, const void* feat_ok, int k_cols,
+static int h2o_split_reduce(const void* cand, const void* meta, int cap, int F, const void* feat_ok, int k_cols,
                      unsigned long long seed, int level, void* dec, const void* node_ok, const void* fgroup,
                      int cfs, hipStream_t s) {
   hipLaunchKernelGGL(k_split_reduce, dim3(cap), dim3(64), 0, s, (const Cand*)cand, (const int*)meta, F,
@@ -3279,7 +2960,7 @@ int h2o_split_reduce(const void* cand, const void* meta, int cap, int F, const v
   return (int)hipGetLastError();
 }
 
-int h2o_ic_next(const void* next, const void* next_meta, const void* dec, const void* ok_cur, const void* ic_map, int F,
+static int h2o_ic_next(const void* next, const void* next_meta, const void* dec, const void* ok_cur, const void* ic_map, int F,
                 void* ok_next, int cap_next, hipStream_t s) {
   if (cap_next <= 0) return 0;
   hipLaunchKernelGGL(k_ic_next, dim3(cap_next), dim3(64), 0, s, (const Node*)next, (const int*)next_meta,
@@ -3288,17 +2969,10 @@ int h2o_ic_next(const void* next, const void* next_meta, const void* dec, const 
   return (int)hipGetLastError();
 }
 
-static int plan_wave_off() {
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("H2O_PLAN_WAVE"); v = (e && e[0] == '0') ? 1 : 0; }
-  return v;
-}
-
 static int plan_launch(const void* nodes, const void* meta, void* dec, void* node_nl, const void* prev_nl, void* curs,
                        void* child_l, void* child_r, void* next, void* next_tile_prefix, void* next_meta,
                        void* next_build_prefix, void* counters, void* scratch, int depth, int max_depth, double min_w,
                        int cap_next, int leaf_cap, PlanReduce pr, hipStream_t s) {
-  pr.no_wave = plan_wave_off();
   hipLaunchKernelGGL(k_plan, dim3(1), dim3(1024), 0, s, (const Node*)nodes, (const int*)meta, (Dec*)dec,
                      (int*)node_nl, (const int*)prev_nl, (int4*)curs, (int*)child_l, (int*)child_r, (Node*)next,
                      (int*)next_tile_prefix, (int*)next_meta, (int*)next_build_prefix, (int*)counters, (int*)scratch,
@@ -3306,31 +2980,8 @@ static int plan_launch(const void* nodes, const void* meta, void* dec, void* nod
   return (int)hipGetLastError();
 }
 
-int h2o_plan(const void* nodes, const void* meta, const void* dec, void* node_nl, const void* prev_nl, void* curs,
-             void* child_l, void* child_r, void* next, void* next_tile_prefix, void* next_meta, void* next_build_prefix,
-             void* counters, void* scratch, int depth, int max_depth, double min_w, int cap_next, int leaf_cap,
-             hipStream_t s) {
-  PlanReduce pr{nullptr, 0, nullptr, 0, 0ull, nullptr, nullptr, 0, 0};
-  return plan_launch(nodes, meta, (void*)dec, node_nl, prev_nl, curs, child_l, child_r, next, next_tile_prefix,
-                     next_meta, next_build_prefix, counters, scratch, depth, max_depth, min_w, cap_next, leaf_cap, pr, s);
-}
-
-int h2o_ranges(void* next, const void* curs, void* tp, void* bp, void* meta, hipStream_t s) {
-  hipLaunchKernelGGL(k_ranges, dim3(1), dim3(1024), 0, s, (Node*)next, (const int4*)curs, (int*)tp, (int*)bp,
-                     (int*)meta);
-  return (int)hipGetLastError();
-}
-
-int h2o_zero_hist(void* hist, const void* next, const void* meta, int cap, int slot_doubles, hipStream_t s) {
-  const int gx = (slot_doubles + 1023) / 1024;
-  hipLaunchKernelGGL(k_zero_hist, dim3(gx < 64 ? gx : 64, cap), dim3(256), 0, s, (double*)hist,
-                     (const Node*)next, (const int*)meta, slot_doubles);
-  return (int)hipGetLastError();
-}
-
-
 // out_f32: write the packed slices as fp32 (the wire format of the sliced exchange)
-int h2o_hist_pack(const void* src, int slot, int F, int Fs, int W, int n, void* dst, int out_f32, hipStream_t s) {
+static int h2o_hist_pack(const void* src, int slot, int F, int Fs, int W, int n, void* dst, int out_f32, hipStream_t s) {
   if (n <= 0) return 0;
   const long long total = (long long)W * n * ((long long)Fs * 2 * NBIN + Fs + 1);
   long long g = (total + 255) / 256;
@@ -3342,14 +2993,8 @@ int h2o_hist_pack(const void* src, int slot, int F, int Fs, int W, int n, void* 
   return (int)hipGetLastError();
 }
 
-static bool route_generic() {   // H2O_ROUTE_GENERIC=1: byte-load path (A/B measurements)
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("H2O_ROUTE_GENERIC"); v = (e && e[0] == '1') ? 1 : 0; }
-  return v == 1;
-}
-
+// 16-byte vectors of a row the route / leaf kernels keep in registers; 0 (any other stride): the byte-load kernels
 static int nv_of(int stride) {
-  if (route_generic()) return 0;
   return stride == 64 ? 4 : stride == 48 ? 3 : stride == 32 ? 2 : stride == 16 ? 1 : 0;
 }
 
@@ -3384,35 +3029,25 @@ static int route_launch(const void* sbins, const void* say, const void* saw, voi
   return (int)hipGetLastError();
 }
 
-int h2o_route(const void* sbins, const void* say, const void* saw, void* dbins, void* day, void* daw, int stride,
-              const void* nodesA, const void* tpA, const void* metaA, const void* decA, const void* clA,
-              const void* crA, const void* decB, const void* clB, const void* crB, void* curs, int tiles_cap,
-              long long N, int planar, int lp, void* lvl2, const void* fdir, hipStream_t s) {
-  return route_launch(sbins, say, saw, dbins, day, daw, stride, nodesA, tpA, metaA, decA, clA, crA, decB, clB, crB,
-                      curs, tiles_cap, N, planar, lp, lvl2, fdir, RangesOut{nullptr, nullptr, nullptr, nullptr, nullptr},
-                      s);
-}
-
 // leaf id of every row (original order) + fixed-point leaf sums -> fp64 leafsum[leaf_cap][2]
 static int leaf_assign_launch(const void* master, int stride, long long N, const void* lvptrs, int D, const void* an,
                               const void* ad, const void* qs, void* leaf_of_row, void* leafq, int leaf_cap,
                               void* leafsum, int n_nodes, int planar, LeafVals lv, hipStream_t s,
-                              const void* lvl2 = nullptr, int* done = nullptr, int grp = 0) {
+                              const void* lvl2, int grp) {
   if (D > TP_MAXL_DEV) return (int)hipErrorInvalidValue;
   long long grid = (N + 255) / 256;
   if (grid > 2048) grid = 2048;
   if (grid < 1) grid = 1;
   const size_t lds = (leaf_cap <= LEAF_LDS_MAX ? (size_t)16 * leaf_cap : 0) +
                      (n_nodes <= LEAF_TREE_MAX ? (size_t)16 * n_nodes : 0);
-#define LA(NV) do { if (done) { LA1(NV, true); } else { LA1(NV, false); } } while (0)
-#define LA1(NV, FU) do { if (grp) { LA2(NV, FU, true); } else { LA2(NV, FU, false); } } while (0)
-#define LA2(NV, FU, G) hipLaunchKernelGGL((k_leaf_assign<NV, FU, G>), dim3((unsigned)grid), dim3(256), lds, s, (const uint8_t*)master, \
-                                  stride, N, (const LevelPtrs*)lvptrs, D, (const float*)an, (const float*)ad,          \
-                                  (const double*)qs, (int*)leaf_of_row, (unsigned long long*)leafq, leaf_cap, n_nodes, planar, \
-                                  (const uint8_t*)lvl2, (double*)leafsum, lv, done)
+#define LA(NV) do { if (grp) { LA2(NV, true); } else { LA2(NV, false); } } while (0)
+#define LA2(NV, G)                                                                                                 \
+  hipLaunchKernelGGL((k_leaf_assign<NV, G>), dim3((unsigned)grid), dim3(256), lds, s, (const uint8_t*)master,     \
+                     stride, N, (const LevelPtrs*)lvptrs, D, (const float*)an, (const float*)ad, (const double*)qs, \
+                     (int*)leaf_of_row, (unsigned long long*)leafq, leaf_cap, n_nodes, planar, (const uint8_t*)lvl2)
   // planar rows of more than two planes: with the root route's level-2 positions (narrow levels below) only the
   // first plane in registers, else the first two; split bytes of later planes are loaded per level
-  switch ((planar && stride > 64 && !route_generic()) ? (lvl2 ? 2 : 4) : nv_of(stride)) {
+  switch ((planar && stride > 64) ? (lvl2 ? 2 : 4) : nv_of(stride)) {
     case 4: LA(4); break;
     case 3: LA(3); break;
     case 2: LA(2); break;
@@ -3420,23 +3055,13 @@ static int leaf_assign_launch(const void* master, int stride, long long N, const
     default: LA(0);
   }
 #undef LA
-#undef LA1
 #undef LA2
-  if (!done)
-    hipLaunchKernelGGL(k_leafsum_finish, dim3((leaf_cap + 255) / 256), dim3(256), 0, s, (unsigned long long*)leafq,
-                       (const double*)qs, leaf_cap, (double*)leafsum, lv);
+  hipLaunchKernelGGL(k_leafsum_finish, dim3((leaf_cap + 255) / 256), dim3(256), 0, s, (unsigned long long*)leafq,
+                     (const double*)qs, leaf_cap, (double*)leafsum, lv);
   return (int)hipGetLastError();
 }
 
-int h2o_leaf_assign(const void* master, int stride, long long N, const void* lvptrs, int D, const void* an,
-                    const void* ad, const void* qs, void* leaf_of_row, void* leafq, int leaf_cap, void* leafsum,
-                    int n_nodes, int planar, hipStream_t s) {
-  const LeafVals lv{0, 0.0, 0.0, 0.0, 0.0, 0.0, nullptr};
-  return leaf_assign_launch(master, stride, N, lvptrs, D, an, ad, qs, leaf_of_row, leafq, leaf_cap, leafsum, n_nodes,
-                            planar, lv, s);
-}
-
-int h2o_amax(const void* aux, long long N, void* amax_bits, hipStream_t s) {
+extern "C" int h2o_amax(const void* aux, long long N, void* amax_bits, hipStream_t s) {
   long long grid = (N + 255) / 256;
   if (grid > 2048) grid = 2048;
   if (grid < 1) grid = 1;
@@ -3446,8 +3071,8 @@ int h2o_amax(const void* aux, long long N, void* amax_bits, hipStream_t s) {
 
 // Tree snapshot to pinned host memory from a kernel (the arena's 16-byte words stored straight into the mapped
 // host buffer) instead of a runtime device-to-host copy. (r5 A/B: the runtime copy started ~12 us after the last
-// tree kernel in every tree.)
-__global__ __launch_bounds__(256) void k_snap_copy(const uint4* __restrict__ src, uint4* __restrict__ dst, long long n16,
+// tree kernel in every tree.) (extern "C": the symbol keeps the plain name it has in the recorded traces)
+extern "C" __global__ __launch_bounds__(256) void k_snap_copy(const uint4* __restrict__ src, uint4* __restrict__ dst, long long n16,
                                                    const unsigned char* __restrict__ srcb, unsigned char* __restrict__ dstb,
                                                    long long nbytes) {
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += (long long)gridDim.x * blockDim.x)
@@ -3457,14 +3082,14 @@ __global__ __launch_bounds__(256) void k_snap_copy(const uint4* __restrict__ src
 }
 
 // device address of a pinned host buffer (hipHostGetDevicePointer); nonzero return: not mapped for the device
-int h2o_host_dev_ptr(void* host, unsigned long long* out) {
+extern "C" int h2o_host_dev_ptr(void* host, unsigned long long* out) {
   void* d = nullptr;
   const hipError_t e = hipHostGetDevicePointer(&d, host, 0);
   *out = (unsigned long long)(uintptr_t)d;
   return (int)e;
 }
 
-int h2o_snap_copy(const void* src, void* dst, long long nbytes, hipStream_t s) {
+extern "C" int h2o_snap_copy(const void* src, void* dst, long long nbytes, hipStream_t s) {
   if (nbytes <= 0) return 0;
   if ((((uintptr_t)src) | ((uintptr_t)dst)) & 15) return (int)hipErrorInvalidValue;
   const long long n16 = nbytes / 16;
@@ -3476,12 +3101,12 @@ int h2o_snap_copy(const void* src, void* dst, long long nbytes, hipStream_t s) {
   return (int)hipGetLastError();
 }
 
-int h2o_qscale(void* amax_bits, void* qs, void* counters, long long N, int fpack, hipStream_t s) {
+extern "C" int h2o_qscale(void* amax_bits, void* qs, void* counters, long long N, int fpack, hipStream_t s) {
   hipLaunchKernelGGL(k_qscale, dim3(1), dim3(256), 0, s, (unsigned*)amax_bits, (double*)qs, (int*)counters, N, fpack);
   return (int)hipGetLastError();
 }
 
-int h2o_bin_assign(const void* X, long long N, int F, int stride, const void* edges, int max_edges,
+extern "C" int h2o_bin_assign(const void* X, long long N, int F, int stride, const void* edges, int max_edges,
                    const void* nedges, const void* iscat, void* bins, int planar, const void* xmap,
                    hipStream_t s) {
   if (planar && (stride % 32 != 0 || stride < 64)) return (int)hipErrorInvalidValue;
@@ -3545,7 +3170,6 @@ struct TreePlan {
   int cand_fs;                // features per rank of the rank-major candidate all-gather (sliced)
   int dist;                   // row-sharded (h2o_tree_dist): build slots go out in the exchange's layout
   void *hsend, *cand_all, *lsx;  // [W][n][E] packed send slots, [W][cap][Fs] candidates, leaf sums + root weight
-  void* fine_f;               // [F] int32: columns of word-aligned 4-column wide numeric groups (or null)
   // narrow levels of wide numeric bins (ops/binning.py layout: columns [0, lo_F) hold every feature's first
   // column, [lo_F, mid_F) the subsets that halve the edge spacing, the rest follow): from level lo_from on
   // (adaptive bin count <= 256) only columns < lo_F, from mid_from on (<= 512) only columns < mid_F are
@@ -3584,8 +3208,8 @@ static inline void tp_node_range(const TreePlan* P, int d, const void* hprev, Sp
 enum { H2O_COLL_ALLREDUCE = 0, H2O_COLL_REDUCE_SCATTER = 1, H2O_COLL_ALLGATHER = 2 };
 enum { H2O_DT_F32 = 0, H2O_DT_F64 = 1, H2O_DT_U8 = 2 };
 // count: ALLREDUCE elements, REDUCE_SCATTER elements received per rank, ALLGATHER elements sent per rank
-typedef int (*h2o_coll_fn)(void* ctx, int op, const void* send, void* recv, long long count, int dtype,
-                           hipStream_t s);
+extern "C" typedef int (*h2o_coll_fn)(void* ctx, int op, const void* send, void* recv, long long count, int dtype,
+                                      hipStream_t s);
 
 static inline const float* tp_aux(const TreePlan* P, int c) { return (const float*)P->aux + (size_t)c * P->N; }
 
@@ -3609,23 +3233,17 @@ static inline void* tp_lvl2(const TreePlan* P) {
   return (P->lvl2 && P->planar && P->D > 2 && tp_fcut(P, 2) > 0 && tp_fcut(P, 2) <= FTILE) ? P->lvl2 : nullptr;
 }
 
-// fused: the route's last block also turns the final cursors into level e+2's ranges and tile prefixes (k_ranges)
-static bool route_fused_ranges() {
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("H2O_ROUTE_RANGES"); v = (e && e[0] == '0') ? 0 : 1; }
-  return v == 1;
-}
-
-static int tp_route(const TreePlan* P, int e, hipStream_t s, bool ranges) {
+// the route of even level e; its last block turns the final cursors into level e + 2's ranges and tile prefixes
+// (RangesOut; the ticket is counters[1])
+static int tp_route(const TreePlan* P, int e, hipStream_t s) {
   const void *sb, *sy, *sw;
   tp_level_buf(P, e, sb, sy, sw);
   const int di = (e / 2) % 2;
   // rows of level e + 2 (and below) are read by narrow levels only: move just the low planes
   const int np = tp_planes(tp_fcut(P, e + 2));
   const int lp = (P->planar && np <= 2) ? np : 0;
-  const RangesOut ro = ranges ? RangesOut{(Node*)P->nodes[e + 2], (int*)P->tp[e + 2], (int*)P->bp[e + 2],
-                                          (int*)P->meta[e + 2], (int*)P->counters + 1}
-                              : RangesOut{nullptr, nullptr, nullptr, nullptr, nullptr};
+  const RangesOut ro{(Node*)P->nodes[e + 2], (int*)P->tp[e + 2], (int*)P->bp[e + 2], (int*)P->meta[e + 2],
+                     (int*)P->counters + 1};
   return route_launch(sb, sy, sw, P->bb[di], P->by[di], P->unit ? nullptr : P->bw[di], P->stride, P->nodes[e], P->tp[e],
                       P->meta[e], P->dec[e], P->cl[e], P->cr[e], P->dec[e + 1], P->cl[e + 1], P->cr[e + 1],
                       P->cur[e + 1], P->tiles_cap[e], P->N, P->planar, lp, e == 0 ? tp_lvl2(P) : nullptr,
@@ -3634,11 +3252,11 @@ static int tp_route(const TreePlan* P, int e, hipStream_t s, bool ranges) {
 
 #define TP_CHECK(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
 
-int h2o_tree_plan_size() { return (int)sizeof(TreePlan); }
+extern "C" int h2o_tree_plan_size() { return (int)sizeof(TreePlan); }
 
 // qscale reset + root histogram (into hist0; the caller all-reduces it when row-sharded; sliced: into
 // hbuild slot 0, which the caller packs and reduce-scatters into hist0)
-int h2o_tree_root(const TreePlan* P, hipStream_t s) {
+extern "C" int h2o_tree_root(const TreePlan* P, hipStream_t s) {
   if (P->D >= TP_MAXL - 1) return (int)hipErrorInvalidValue;
   if (P->compute_amax) TP_CHECK(h2o_amax(P->aux, P->N, P->amax_bits, s));
   TP_CHECK(h2o_qscale(P->amax_bits, P->qs, P->counters, P->N, P->packed == 2, s));
@@ -3647,9 +3265,9 @@ int h2o_tree_root(const TreePlan* P, hipStream_t s) {
     TP_CHECK(h2o_hist_root16(P->fine16, P->f16_planes, P->unit ? nullptr : tp_aux(P, 0), tp_aux(P, 1), P->N, P->meta[0],
                              P->f16col, P->f16n, P->F, P->partials, P->slot, P->qs, g0, P->pf32, s));
   else
-  TP_CHECK(h2o_hist_build(P->master, P->stride, P->unit ? nullptr : tp_aux(P, 0), tp_aux(P, 1), P->nodes[0], P->bp[0],
-                          P->meta[0], P->F, P->partials, P->slot, P->qs, g0, P->packed, nullptr, nullptr, P->pf32, P->N,
-                          P->planar | (P->no_na << 1), P->nbins_f, P->fine_f, tp_planes(tp_fcut(P, 0)), nullptr, s));
+    TP_CHECK(h2o_hist_build(P->master, P->stride, P->unit ? nullptr : tp_aux(P, 0), tp_aux(P, 1), P->nodes[0], P->bp[0],
+                            P->meta[0], P->F, P->partials, P->slot, P->qs, g0, P->packed, nullptr, nullptr, P->pf32,
+                            P->N, P->planar | (P->no_na << 1), P->nbins_f, tp_planes(tp_fcut(P, 0)), nullptr, s));
   // row-sharded all-reduce: straight into the wire buffer; sliced: hbuild (packed by slice next)
   if (P->dist && !P->sliced)
     return h2o_hist_reduce(P->partials, P->slot, P->used, P->nodes[0], P->bp[0], P->meta[0], 1, g0, P->hrecv, nullptr,
@@ -3661,7 +3279,7 @@ int h2o_tree_root(const TreePlan* P, hipStream_t s) {
 
 // split search of level d: every feature into cand, or (sliced) this rank's feature slice into cand_local.
 // Row-sharded: the level's node histograms are derived from the exchanged build slots on the way (Derive).
-int h2o_tree_find(const TreePlan* P, int d, hipStream_t s) {
+static int h2o_tree_find(const TreePlan* P, int d, hipStream_t s) {
   void* hc = (d % 2) ? P->hist1 : P->hist0;
   const void* hp = (d % 2) ? P->hist0 : P->hist1;      // level d-1 (unused at the root: build = 1)
   SplitParams p;
@@ -3685,46 +3303,7 @@ int h2o_tree_find(const TreePlan* P, int d, hipStream_t s) {
 
 // decisions (from cand) + plan, then the next level's histogram.
 // returns 0 = histogram done (dist: compact buffer ready for the collective), 1 = last level, <0 error.
-static int tree_grow(const TreePlan* P, int d, int dist, hipStream_t s, bool plan_done);
-int h2o_tree_grow(const TreePlan* P, int d, int dist, hipStream_t s) { return tree_grow(P, d, dist, s, false); }
-
-// single-process levels of <= PLAN_REDUCE_MAX nodes: split search + plan in one launch (k_split_find_plan). OFF by
-// default (H2O_PLAN_FUSED=1 turns it on). MEASURED r5 (scripts/gpu_r5_c15.sh, 11M HIGGS): the per-block agent-scope
-// release (buffer_wbl2) of the ticket made k_split_find_plan 16-43 us per level against 13-19 for the two launches,
-// and the tree 1.262 -> 1.372 ms (24 dispatches instead of 31): on MI355X an L2 write-back per block costs far more
-// than a kernel boundary.
-static bool plan_fused() {
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("H2O_PLAN_FUSED"); v = (e && e[0] == '1') ? 1 : 0; }
-  return v == 1;
-}
-
-static int tree_find_plan(const TreePlan* P, int d, hipStream_t s) {
-  void* hc = (d % 2) ? P->hist1 : P->hist0;
-  SplitParams p;
-  p.min_w = P->min_w; p.min_split_improvement = P->msi; p.lambda = P->lam; p.alpha = P->alpha; p.gamma = P->gamma;
-  p.mode = P->mode; p.random_split = P->random_split; p.seed = P->seed; p.hist_type = P->hist_type;
-  p.fcut = tp_fcut(P, d);
-  tp_node_range(P, d, (d % 2) ? P->hist0 : P->hist1, p);
-  const int cap = P->caps[d];
-  const int kc = P->kc_level[d] > 0 ? P->kc_level[d] : P->k_cols;
-  const PlanReduce pr{(const Cand*)P->cand, P->F, (const int*)P->feat_ok, kc, P->seed,
-                      P->ic_map ? (const unsigned char*)P->ic[d] : nullptr, (const int*)P->fgroup, 0, cap};
-  const bool odd = d % 2 == 1;
-  const PlanArgs pa{(const Node*)P->nodes[d], (const int*)P->meta[d], (Dec*)P->dec[d], (int*)P->nl[d],
-                    odd ? (const int*)P->nl[d - 1] : nullptr, (int4*)P->cur[d], (int*)P->cl[d], (int*)P->cr[d],
-                    (Node*)P->nodes[d + 1], (int*)P->tp[d + 1], (int*)P->meta[d + 1], (int*)P->bp[d + 1],
-                    (int*)P->counters, (int*)P->scratch, d, P->D, P->caps[d + 1], P->leaf_cap, P->min_w, pr,
-                    (int*)P->counters + 2};
-  if (P->F <= 0 || cap <= 0) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_split_find_plan, dim3(cap, P->F), dim3(256), 0, s, (double*)hc, P->slot, (const int*)P->meta[d],
-                     P->F, (const int*)P->nbins_f, (const int*)P->iscat_f, (const int*)P->mono_f, p, d,
-                     (Cand*)P->cand, d == 0 ? (double*)P->rootw : nullptr, (const float*)P->edges, P->nb_level[d], 0,
-                     P->F, Derive{nullptr, 0, 0, nullptr, nullptr}, pa);
-  return (int)hipGetLastError();
-}
-
-static int tree_grow(const TreePlan* P, int d, int dist, hipStream_t s, bool plan_done) {
+static int h2o_tree_grow(const TreePlan* P, int d, int dist, hipStream_t s) {
   void* hc = (d % 2) ? P->hist1 : P->hist0;
   void* hn = (d % 2) ? P->hist0 : P->hist1;
   const int cap = P->caps[d];
@@ -3737,19 +3316,17 @@ static int tree_grow(const TreePlan* P, int d, int dist, hipStream_t s, bool pla
   const int cfs = P->sliced ? P->cand_fs : 0;
   PlanReduce pr{nullptr, P->F, (const int*)P->feat_ok, kc, P->seed,
                 P->ic_map ? (const unsigned char*)P->ic[d] : nullptr, (const int*)P->fgroup, cfs, cap};
-  if (!plan_done) {
-    if (cap <= PLAN_REDUCE_MAX) {
-      pr.cand = (const Cand*)cand;
-    } else {
-      rc = h2o_split_reduce(cand, P->meta[d], cap, P->F, P->feat_ok, kc, P->seed, d, P->dec[d],
-                            P->ic_map ? P->ic[d] : nullptr, P->fgroup, cfs, s);
-      if (rc) return -rc;
-    }
-    rc = plan_launch(P->nodes[d], P->meta[d], P->dec[d], P->nl[d], odd ? P->nl[d - 1] : nullptr, P->cur[d], P->cl[d],
-                     P->cr[d], P->nodes[d + 1], P->tp[d + 1], P->meta[d + 1], P->bp[d + 1], P->counters, P->scratch,
-                     d, P->D, P->min_w, P->caps[d + 1], P->leaf_cap, pr, s);
+  if (cap <= PLAN_REDUCE_MAX) {
+    pr.cand = (const Cand*)cand;
+  } else {
+    rc = h2o_split_reduce(cand, P->meta[d], cap, P->F, P->feat_ok, kc, P->seed, d, P->dec[d],
+                          P->ic_map ? P->ic[d] : nullptr, P->fgroup, cfs, s);
     if (rc) return -rc;
   }
+  rc = plan_launch(P->nodes[d], P->meta[d], P->dec[d], P->nl[d], odd ? P->nl[d - 1] : nullptr, P->cur[d], P->cl[d],
+                   P->cr[d], P->nodes[d + 1], P->tp[d + 1], P->meta[d + 1], P->bp[d + 1], P->counters, P->scratch,
+                   d, P->D, P->min_w, P->caps[d + 1], P->leaf_cap, pr, s);
+  if (rc) return -rc;
   if (P->ic_map && d + 1 < P->D) {
     rc = h2o_ic_next(P->nodes[d + 1], P->meta[d + 1], P->dec[d], P->ic[d], P->ic_map, P->F, P->ic[d + 1],
                      P->caps[d + 1], s);
@@ -3765,9 +3342,7 @@ static int tree_grow(const TreePlan* P, int d, int dist, hipStream_t s, bool pla
     // level 1 of a narrow planar run: the root split's side of every row as bytes (read by the level-1
     // histogram blocks and the root route instead of the split column's plane)
     const void* fdir = nullptr;
-    // (also every planar run whose level 1 builds >= 2 planes, e.g. XGBoost 100M x 50: each plane's histogram blocks
-    // would otherwise read the root split column's plane once per plane)
-    if (d == 0 && P->fdir && (tp_lvl2(P) || (P->planar && tp_planes(tp_fcut(P, 1) > 0 ? tp_fcut(P, 1) : P->F) >= 2))) {
+    if (d == 0 && P->fdir && tp_lvl2(P)) {
       long long g = (P->N + 255) / 256;
       if (g > 4096) g = 4096;
       if (g < 1) g = 1;
@@ -3779,21 +3354,16 @@ static int tree_grow(const TreePlan* P, int d, int dist, hipStream_t s, bool pla
     }
     rc = h2o_hist_build(sb, P->stride, sw, sy, P->nodes[d + 1], P->bp[d + 1], P->meta[d + 1], P->F, P->partials,
                         P->slot, P->qs, gh, P->packed, P->dec[d], P->nl[d], P->pf32, P->N, P->planar | (P->no_na << 1),
-                        P->nbins_f, P->fine_f, tp_planes(tp_fcut(P, d + 1)), fdir, s);
+                        P->nbins_f, tp_planes(tp_fcut(P, d + 1)), fdir, s);
   } else {
     // regroup level d-1's rows two levels down, then histogram level d+1 (even) contiguously
-    const bool fused = route_fused_ranges() && P->tiles_cap[d - 1] > 0;
-    rc = tp_route(P, d - 1, s, fused);
+    rc = tp_route(P, d - 1, s);
     if (rc) return -rc;
-    if (!fused) {
-      rc = h2o_ranges(P->nodes[d + 1], P->cur[d], P->tp[d + 1], P->bp[d + 1], P->meta[d + 1], s);
-      if (rc) return -rc;
-    }
     gh = P->tiles_cap[d + 1] < P->grid ? P->tiles_cap[d + 1] : P->grid;
     tp_level_buf(P, d + 1, sb, sy, sw);
     rc = h2o_hist_build(sb, P->stride, sw, sy, P->nodes[d + 1], P->bp[d + 1], P->meta[d + 1], P->F, P->partials,
                         P->slot, P->qs, gh, P->packed, nullptr, nullptr, P->pf32, P->N, P->planar | (P->no_na << 1),
-                        P->nbins_f, P->fine_f, tp_planes(tp_fcut(P, d + 1)), nullptr, s);
+                        P->nbins_f, tp_planes(tp_fcut(P, d + 1)), nullptr, s);
   }
   if (rc) return -rc;
   const int lo = tp_fcut(P, d + 1);
@@ -3810,11 +3380,10 @@ static int tree_grow(const TreePlan* P, int d, int dist, hipStream_t s, bool pla
 }
 
 // one level: split search, decisions, plan, next histogram (single process and all-reduce mode)
-int h2o_tree_level(const TreePlan* P, int d, int dist, hipStream_t s) {
-  const bool fuse = !dist && !P->dist && !P->sliced && P->caps[d] <= PLAN_REDUCE_MAX && plan_fused() && !P->gcat;
-  const int rc = fuse ? tree_find_plan(P, d, s) : h2o_tree_find(P, d, s);
+static int h2o_tree_level(const TreePlan* P, int d, int dist, hipStream_t s) {
+  const int rc = h2o_tree_find(P, d, s);
   if (rc) return -rc;
-  return tree_grow(P, d, dist, s, fuse);
+  return h2o_tree_grow(P, d, dist, s);
 }
 
 
@@ -3824,16 +3393,12 @@ static int tree_leaves(const TreePlan* P, bool values, hipStream_t s) {
   for (int d = 0; d < P->D; ++d) n_nodes += P->caps[d];
   const LeafVals lv{P->log_link, P->scale, P->kclamp, P->mx, P->leaf_lam, P->leaf_l1,
                     values ? (float*)P->leafval : nullptr};
-  // (H2O_LEAF_FUSED=1: k_leafsum_finish in the leaf-assign launch's last block. OFF by default — MEASURED r5: the
-  // 2048 per-block release fences made k_leaf_assign 221 us against 115 + 4 for the two launches)
-  static int fused = -1;
-  if (fused < 0) { const char* e = getenv("H2O_LEAF_FUSED"); fused = (e && e[0] == '1') ? 1 : 0; }
   return leaf_assign_launch(P->master, P->stride, P->N, P->lvptrs, P->D, tp_aux(P, P->num_plane), tp_aux(P, 3), P->qs,
                             P->leaf_of_row, P->leafq, P->leaf_cap, P->leafsum, n_nodes, P->planar, lv, s, tp_lvl2(P),
-                            fused ? (int*)P->counters + 3 : nullptr, P->gcat != nullptr);
+                            P->gcat != nullptr);
 }
 
-int h2o_tree_leaves(const TreePlan* P, hipStream_t s) { return tree_leaves(P, false, s); }
+static int h2o_tree_leaves(const TreePlan* P, hipStream_t s) { return tree_leaves(P, false, s); }
 
 static inline int coll(const TreePlan* P, int op, const void* snd, void* rcv, long long count, int dt, hipStream_t s) {
   return ((h2o_coll_fn)P->coll_fn)(P->coll_ctx, op, snd, rcv, count, dt, s);
@@ -3865,7 +3430,7 @@ static int exchange(const TreePlan* P, int n, hipStream_t s) {
 //    collectives per level.
 // Both end with one all-reduce of the leaf sums (sliced: + the root weight, which only the owner of feature 0
 // computes).
-int h2o_tree_dist(const TreePlan* P, hipStream_t s) {
+extern "C" int h2o_tree_dist(const TreePlan* P, hipStream_t s) {
   if (!P->coll_fn || P->W < 1) return (int)hipErrorInvalidValue;
   if (!P->dist) return (int)hipErrorInvalidValue;
   TP_CHECK(h2o_tree_root(P, s));               // -> hbuild slot 0 (sliced) / hrecv slot 0
@@ -3902,7 +3467,7 @@ int h2o_tree_dist(const TreePlan* P, hipStream_t s) {
 }
 
 // single process: the whole tree (root .. leaves, and leaf_native values in the leaf-sum pass) in one host call
-int h2o_tree_all(const TreePlan* P, hipStream_t s) {
+extern "C" int h2o_tree_all(const TreePlan* P, hipStream_t s) {
   TP_CHECK(h2o_tree_root(P, s));
   for (int d = 0; d < P->D; ++d) {
     const int r = h2o_tree_level(P, d, 0, s);
@@ -3912,5 +3477,3 @@ int h2o_tree_all(const TreePlan* P, hipStream_t s) {
   return tree_leaves(P, P->leaf_native != 0, s);
 }
 #undef TP_CHECK
-
-}  // extern "C"

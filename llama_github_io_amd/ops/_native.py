@@ -24,10 +24,6 @@ _HIP_SIGS = {
     "h2o_tree_sizes": [c_void_p],
     "h2o_tree_plan_size": [],
     "h2o_tree_root": [c_void_p, c_void_p],
-    "h2o_tree_level": [c_void_p, c_int, c_int, c_void_p],
-    "h2o_tree_find": [c_void_p, c_int, c_void_p],
-    "h2o_tree_grow": [c_void_p, c_int, c_int, c_void_p],
-    "h2o_hist_pack": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p],
     "h2o_tree_dist": [c_void_p, c_void_p],
     "h2o_rccl_load": [ctypes.c_char_p],
     "h2o_rccl_version": [],
@@ -37,22 +33,6 @@ _HIP_SIGS = {
     "h2o_rccl_destroy": [c_void_p, c_int],
     "h2o_rccl_coll": [c_void_p, c_int, c_void_p, c_void_p, c_ll, c_int, c_void_p],
     "h2o_tree_all": [c_void_p, c_void_p],
-    "h2o_tree_leaves": [c_void_p, c_void_p],
-    "h2o_hist_build": [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p,
-                       c_int, c_int, c_void_p, c_void_p, c_int, c_ll, c_int, c_void_p, c_void_p, c_int, c_void_p,
-                       c_void_p],
-    "h2o_split_find": [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_double, c_double,
-                       c_double, c_double, c_double, c_int, c_int, c_ull, c_int, c_void_p, c_void_p, c_void_p, c_int,
-                       c_int, c_int, c_int, c_void_p],
-    "h2o_split_reduce": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_ull, c_int, c_void_p, c_void_p, c_void_p,
-                         c_int, c_void_p],
-    "h2o_ic_next": [c_void_p] * 6 + [c_int, c_void_p, c_int, c_void_p],
-    "h2o_plan": [c_void_p] * 14 + [c_int, c_int, c_double, c_int, c_int, c_void_p],
-    "h2o_ranges": [c_void_p] * 6,
-    "h2o_zero_hist": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p],
-    "h2o_route": [c_void_p] * 6 + [c_int] + [c_void_p] * 10 + [c_int, c_ll, c_int, c_int, c_void_p, c_void_p, c_void_p],
-    "h2o_leaf_assign": [c_void_p, c_int, c_ll, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                        c_void_p, c_int, c_int, c_void_p],
     "h2o_bin_assign": [c_void_p, c_ll, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                        c_void_p],
     "h2o_amax": [c_void_p, c_ll, c_void_p, c_void_p],
@@ -65,9 +45,6 @@ _HIP_SIGS = {
     "h2o_snap_copy": [c_void_p, c_void_p, c_ll, c_void_p],
     "h2o_fine16_build": [c_void_p, c_int, c_ll, c_void_p, c_int, c_void_p, c_void_p],
     "h2o_host_dev_ptr": [c_void_p, c_void_p],
-    "h2o_hist_reduce": [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
-                        c_void_p, c_int, c_int, c_int, c_int, c_void_p],
-    "h2o_leaf_values": [c_void_p, c_int, c_int, c_double, c_double, c_double, c_double, c_double, c_void_p, c_void_p],
     "h2o_gbm_step": [c_ll, c_ll, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_float, c_ull,
                      ctypes.c_float, c_void_p, c_void_p, c_int, c_void_p],
     "h2o_add_leaf": [c_ll, c_void_p, c_int, c_void_p, c_void_p, c_void_p],
@@ -77,7 +54,7 @@ _HIP_SIGS = {
 # Bumped whenever a C launcher's argument list changes; every native library exports h2o_abi_version()
 # (csrc/abi.h) and a library built from older sources is refused instead of being called with shifted
 # arguments.
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 
 def _check_abi(lib, name: str) -> None:
@@ -89,10 +66,13 @@ def _check_abi(lib, name: str) -> None:
 
 
 def _bind(lib, sigs):
+    missing = [name for name in sigs if not hasattr(lib, name)]
+    if missing:
+        # a signature without a symbol is stale: the launcher was renamed or removed in csrc
+        raise RuntimeError(f"libh2o_hip exports no {', '.join(sorted(missing))}: remove the stale signature(s) or "
+                           "rebuild with `python -m llama_github_io_amd.build_native --force`")
     for name, args in sigs.items():
-        fn = getattr(lib, name, None)
-        if fn is None:
-            continue
+        fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = c_int
     return lib

@@ -26,7 +26,6 @@ exact. Decoding maps the bitset back through ``level_to_bin`` to a bitset over t
 """
 from __future__ import annotations
 
-import os
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -235,10 +234,7 @@ def fit_binning(X: torch.Tensor, iscat, nlevels=None, max_bins: int = MAX_DATA_B
         # these halve the edge spacing: e[0::4] + e[2::4] = e[0::2]), then those odd subsets. From the level on
         # where the adaptive bin count drops to 512 the tree searches only the first two tiers (n_mid columns),
         # from 256 only the first (n_low; ops/tree.narrow_cut): only their planes are histogrammed and moved.
-        # H2O_HIST_FINE=1 keeps the former layout instead: the features of exactly 4 interleaved columns first,
-        # each filling one aligned 4-byte row word (one fine-bin atomic per row and feature in the histogram kernel).
-        fine_layout = os.environ.get("H2O_HIST_FINE") == "1"
-        quad, rest, low, mid, high, groups = [], [], [], [], [], []
+        low, mid, high, groups = [], [], [], []
         for f in range(F):
             e = edges[f]
             if wide_cat[f]:
@@ -260,18 +256,14 @@ def fit_binning(X: torch.Tensor, iscat, nlevels=None, max_bins: int = MAX_DATA_B
             for k in range(n):
                 ek = e if n == 1 else np.ascontiguousarray(e[k::n])
                 c = (f, ek, (ek.size + 1) if e is not None else nbins[f], l2b[f])
-                (quad if n == 4 else rest).append(c)
                 (low if k == 0 else high if (n == 4 and k % 2) else mid).append(c)
         gcols = [c for g, _ in groups for c in g]
         cat_groups = []
         for i, (_, n) in enumerate(groups):
             cat_groups.append((4 * i, n))
-        if fine_layout:
-            cols = gcols + quad + rest
-        else:
-            cols = gcols + low + mid + high
-            n_low = len(gcols) + len(low) if (mid or high) else 0
-            n_mid = len(gcols) + len(low) + len(mid) if high else 0
+        cols = gcols + low + mid + high
+        n_low = len(gcols) + len(low) if (mid or high) else 0
+        n_mid = len(gcols) + len(low) + len(mid) if high else 0
         pad = np.asarray([len(c) > 4 and c[4] for c in cols], dtype=bool)
         cols = [c[:4] for c in cols]
         vmap = np.asarray([c[0] for c in cols], dtype=np.int32)

@@ -48,21 +48,6 @@ HIST_TYPES = {"auto": HT_UNIFORM, "uniformadaptive": HT_UNIFORM, "random": HT_RA
 _M64 = (1 << 64) - 1
 
 
-def fine_columns(fgroup, iscat, F):
-    """int32 [F]: 1 for the columns of the word-aligned (4m .. 4m+3) groups of exactly 4 engine columns of one
-    numeric feature (wide numeric bins, ops/binning.py) — the histogram kernel adds one fine-bin atomic per row and
-    group there — or None when there is no such group."""
-    if fgroup is None:
-        return None
-    g = np.asarray(fgroup, dtype=np.int64)
-    out = np.zeros(F, dtype=np.int32)
-    for m in range(0, F - 3, 4):
-        if (g[m] == g[m + 1] == g[m + 2] == g[m + 3] and (m == 0 or g[m - 1] != g[m]) and (m + 4 >= F or g[m + 4] != g[m])
-                and not any(int(iscat[m + l]) for l in range(4))):
-            out[m:m + 4] = 1
-    return out if out.any() else None
-
-
 def narrow_cut(p: "SplitParams", n_low: int, n_mid: int, F: int):
     """Columns each level searches under the NARROW views of wide numeric bins: ``(mid_from, lo_from)``, the first
     levels (or -1) from which only engine columns [0, n_mid) resp. [0, n_low) are searched (ops/binning.py three-tier
@@ -731,7 +716,7 @@ class _TreePlan(ctypes.Structure):
                 [("leaf_lam", _cd), ("leaf_l1", _cd)] + [("planar", _ci), ("no_na", _ci)] +
                 [("fgroup", _vp)] + [("coll_fn", _vp), ("coll_ctx", _vp)] +
                 [(n, _ci) for n in ("W", "cf32", "cand_fs", "dist")] + [(n, _vp) for n in ("hsend", "cand_all", "lsx")] +
-                [("fine_f", _vp)] + [(n, _ci) for n in ("lo_F", "lo_from", "mid_F", "mid_from")] + [("lvl2", _vp), ("fdir", _vp)] +
+                [(n, _ci) for n in ("lo_F", "lo_from", "mid_F", "mid_from")] + [("lvl2", _vp), ("fdir", _vp)] +
                 [("num_plane", _ci), ("pad4", _ci)] +
                 [(n, _vp) for n in ("fine16", "f16col", "f16n")] + [("f16_planes", _ci), ("pad5", _ci)] +
                 [("vrange", _vp), ("range_on", _ci), ("pad6", _ci)] + [("gcat", _vp)])
@@ -806,12 +791,8 @@ class GpuTreeBuilder:
         # the only histogram bytes a row-sharded run all-reduces per level
         self.hbuild = torch.empty(max(self.caps[:D]) * self.slot, dtype=torch.float64, device=dev)
         # per-block partial histograms of one level (k_hist_build -> k_hist_reduce): G + nodes slots
-        # (packed histograms fit two blocks per CU; H2O_HIST_BPC=2 launches hist_bpc * grid blocks)
-        # measured: 2 is 3-14 % slower; again with the barrier-free filtered pass (round 3): 11M 1.34 -> 1.40,
-        # 1.375M 0.423 -> 0.474 ms/tree (the doubled partial slots cost more than the extra waves gain)
-        self.hist_bpc = int(os.environ.get("H2O_HIST_BPC", "1"))
         # (zeroed: narrow levels leave the partial entries of columns they do not build untouched)
-        self.partials = torch.zeros((self.hist_bpc * grid + capmax) * self.slot, dtype=torch.float64, device=dev)
+        self.partials = torch.zeros((grid + capmax) * self.slot, dtype=torch.float64, device=dev)
         self.tiles_cap = [(N + T - 1) // T + c for c in self.caps]
         self.cand = torch.empty(capmax * F * CAND_BYTES, dtype=torch.uint8, device=dev)
         self.scratch = torch.empty(2 * capmax + 16, dtype=torch.int32, device=dev)
@@ -823,7 +804,6 @@ class GpuTreeBuilder:
         self.nbins_f = torch.as_tensor(np.asarray(nbins_f, dtype=np.int32), device=dev)
         self.iscat_f = torch.as_tensor(np.asarray(iscat_f, dtype=np.int32), device=dev)
         self.iscat_np = np.asarray(iscat_f, dtype=np.int32)
-        self.fine_f = None
         self.n_low = self.n_mid = 0
         self.mono_f = None if mono_f is None else torch.as_tensor(np.asarray(mono_f, dtype=np.int32), device=dev)
         self.feat_ok_all = torch.ones(F, dtype=torch.int32, device=dev)
@@ -971,13 +951,9 @@ class GpuTreeBuilder:
         self.fgroup = None if enc is None else torch.as_tensor(enc, device=self.dev).contiguous()
         self._fgroup_np = None if fgroup is None else np.asarray(fgroup, dtype=np.int64)
         self._fine16 = None
-        self.fine_f = fine_columns(fgroup, self.iscat_np, self.F)
-        if self.fine_f is not None:
-            self.fine_f = torch.as_tensor(self.fine_f, device=self.dev).contiguous()
         self.n_low, self.n_mid = int(n_low), int(n_mid)
         if getattr(self, "_plan", None) is not None:
             self._plan.fgroup = 0 if self.fgroup is None else self.fgroup.data_ptr()
-            self._plan.fine_f = 0 if self.fine_f is None else self.fine_f.data_ptr()
             self._set_plan_narrow(self._plan)
             self._set_plan_fine16(self._plan)
 
@@ -997,18 +973,12 @@ class GpuTreeBuilder:
         P.mid_F, P.mid_from = (self.n_mid, mid) if mid >= 0 else (0, 0)
         # every row's level-2 position from the root route (the leaf walk starts there; narrow planar runs only)
         # and the root split's side of every row (level 1 reads these bytes instead of the split column's plane)
-        # H2O_ROW_DIR_PLANAR=1: planar runs of >= 2 planes (e.g. XGBoost 100M x 50) also get the root split's side as
-        # bytes for level 1. MEASURED r5 (scripts/gpu_r5_c30.sh): 17.48-17.75 vs 17.53 ms/tree — the second plane's
-        # read of the split column hits the caches; off by default
-        wide = self.planar and self.F > 32 and os.environ.get("H2O_ROW_DIR_PLANAR", "0") == "1"
-        if (lo >= 0 and self.planar) or wide:
-            if getattr(self, "_fdir", None) is None:
-                self._fdir = torch.empty(self.N, dtype=torch.uint8, device=self.dev)
-            if lo >= 0 and getattr(self, "_lvl2", None) is None:
-                self._lvl2 = torch.empty(self.N, dtype=torch.uint8, device=self.dev)
         on = lo >= 0 and self.planar
+        if on and getattr(self, "_fdir", None) is None:
+            self._fdir = torch.empty(self.N, dtype=torch.uint8, device=self.dev)
+            self._lvl2 = torch.empty(self.N, dtype=torch.uint8, device=self.dev)
         P.lvl2 = self._lvl2.data_ptr() if on else 0
-        P.fdir = self._fdir.data_ptr() if (on or wide) else 0
+        P.fdir = self._fdir.data_ptr() if on else 0
 
     def _fine16_map(self):
         """Slot maps of the root pass from 16-bit fine planes (k_hist_root16), or None when it does not apply: the
@@ -1081,7 +1051,7 @@ class GpuTreeBuilder:
         P = _TreePlan()
         p = self.p
         P.N, P.stride, P.F, P.D, P.slot, P.used, P.pf32 = self.N, self.stride, self.F, self.D, self.slot, self.used, self.pf32
-        P.leaf_cap, P.mode, P.random_split = self.leaf_cap, int(p.mode), int(p.random_split)
+        P.grid, P.leaf_cap, P.mode, P.random_split = self.grid, self.leaf_cap, int(p.mode), int(p.random_split)
         P.min_w, P.msi, P.lam, P.alpha, P.gamma = p.min_w, p.min_split_improvement, p.lam, p.alpha, p.gamma
         P.master, P.partials = self.master.data_ptr(), self.partials.data_ptr()
         P.hist0, P.hist1, P.hbuild = self._hp[0], self._hp[1], self.hbuild.data_ptr()
@@ -1114,7 +1084,6 @@ class GpuTreeBuilder:
         P.fgroup = 0 if fg is None else fg.data_ptr()
         gc = getattr(self, "gcat", None)
         P.gcat = 0 if gc is None else gc.data_ptr()
-        P.fine_f = 0 if self.fine_f is None else self.fine_f.data_ptr()     # used only under H2O_HIST_FINE=1
         self._set_plan_narrow(P)
         self._set_plan_fine16(P)
         P.sliced, P.fs0, P.fsn, P.sslot = int(self.sliced), self.fs0, self.fsn, self.sslot
@@ -1198,7 +1167,6 @@ class GpuTreeBuilder:
         P.k_cols, P.packed, P.seed = _level_k(k_cols, 0), (2 if packed == 2 else int(bool(packed))), int(seed) & _M64
         for d in range(_MAXL):
             P.kc_level[d] = _level_k(k_cols, d) if isinstance(k_cols, (list, tuple)) else 0
-        P.grid = self.grid * (self.hist_bpc if packed else 1)
         P.leaf_native = int(leaf_native is not None)
         if leaf_native is not None:
             lg, scale, kclamp, mx = leaf_native[:4]

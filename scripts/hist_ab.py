@@ -57,16 +57,9 @@ def main():
     b = builders[-1]
     out = {"rows": n, "stride": b.stride, "planar": b.planar}
     out["root_us_default"] = time_root(b)
-    os.environ["H2O_HIST_REPL"] = "0"
-    out["root_us_no_replicas"] = time_root(b)
-    del os.environ["H2O_HIST_REPL"]
     os.environ["H2O_HIST_BUF"] = "0"
     out["root_us_no_buf"] = time_root(b)
     del os.environ["H2O_HIST_BUF"]
-    for dbg, tag in (("1", "no_flush"), ("2", "no_atomics"), ("3", "loads_only")):
-        os.environ["H2O_HIST_DBG"] = dbg
-        out["root_us_" + tag] = time_root(b)
-    del os.environ["H2O_HIST_DBG"]
     # data variants: uniform random bins in the real buffer (28 features, zero padding bytes)
     m = b.master
     keep = m.clone()

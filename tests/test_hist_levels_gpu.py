@@ -21,8 +21,8 @@ Which k_hist_build instantiation a case reaches (launch_hist): FILT = every odd 
 !FILT = the even levels; PACKED / UNIT = the case's mode; NONA = the cases without NA rows, with 4 bin replicas on
 columns 1, 2, 5, 6 (3, 60, 7, 1 bins), 2 on column 3 (100 bins), 1 elsewhere (``mode-*-nona``), !NONA = ``mode-*-na``;
 the ``acc`` branch of flush_partial = ``win-*`` and ``pf32-count`` (2 and 4 windows per block). BUF is on for every
-power-of-two row size here and off for strides 12 and 48 (``layout-s12-*``, ``layout-s48-*``); the > 2^31-byte sides of
-BUF and FINE (H2O_HIST_FINE=1) stay with the large-buffer and A/B tests of test_tree_engine.py.
+power-of-two row size here and off for strides 12 and 48 (``layout-s12-*``, ``layout-s48-*``); the > 2^31-byte side of
+BUF stays with the large-buffer test of test_tree_engine.py.
 
 Worst err / tol on an MI355X, per mode and plane, over every case (a ratio above 1 is a failure; the test prints
 the figures of each case as ``HISTRATIO <case> <mode> <plane> <ratio>``):

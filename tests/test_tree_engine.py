@@ -231,12 +231,10 @@ def test_gpu_tree_matches_reference_row_widths(F):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("F", [40, 70])
-@pytest.mark.parametrize("row_dir", ["1", "0"])
-def test_gpu_planar_tree_matches_reference(F, row_dir, monkeypatch):
-    """Planar bins (F > 32, one 32-byte plane per feature tile) as the XGBoost / wide GBM runs use them, with and
-    without the root split's direction bytes for level 1 (H2O_ROW_DIR_PLANAR): decisions and leaves of the fp64
-    reference."""
-    monkeypatch.setenv("H2O_ROW_DIR_PLANAR", row_dir)
+def test_gpu_planar_tree_matches_reference(F):
+    """Planar bins (F > 32, one 32-byte plane per feature tile) as the XGBoost / wide GBM runs use them: decisions and
+    leaves of the fp64 reference. (The root split's direction bytes belong to the narrow planar runs, see
+    test_gpu_wide_bins_match_reference.)"""
     X, y, info = _data(N=30000, F=F, cat=True, seed=F + 1)
     g = torch.Generator().manual_seed(F)
     X[F - 1] = X[0] * 0.5 + torch.randn(X.shape[1], generator=g)
@@ -251,7 +249,7 @@ def test_gpu_planar_tree_matches_reference(F, row_dir, monkeypatch):
     gb = T.GpuTreeBuilder(apply_binning(b, X.to(dev), planar=True), F, b.nbins, b.iscat, None, 6, p)
     assert gb.planar
     gb.build(aux.to(dev), leaf_fn=lambda ls: (ls[:, 0] / ls[:, 1]).float(), packed=True, unit=True)
-    assert bool(gb._plan.fdir) == (row_dir == "1")      # (off by default; the A/B switch keeps its path tested)
+    assert not gb._plan.fdir      # (no narrow levels here: no direction bytes)
     tl_g = gb.pop_levels()[0]
     assert tl_g.n_leaves == tl_r.n_leaves
     for dr, dg in zip(tl_r.decs, tl_g.decs):
@@ -548,25 +546,17 @@ def test_gpu_tree_bins_matrix_above_2pow31_bytes():
     assert torch.equal(ref.leaf_of_row, gb.leaf_of_row.cpu())
 
 
-@pytest.mark.parametrize("fine", ["0", "1"])
-def test_wide_binning_columns_are_interleaved_edge_subsets(fine, monkeypatch):
+def test_wide_binning_columns_are_interleaved_edge_subsets():
     """nbins_top_level = 1024 (SharedTreeModel.java:57): a numeric feature with more than 254 edges is binned
     as engine columns over the edge subsets e[k::n]; every fine threshold is one column's split."""
-    monkeypatch.setenv("H2O_HIST_FINE", fine)
     g = torch.Generator().manual_seed(1)
     X = torch.rand(3, 20000, generator=g)
     X[1] = torch.randint(0, 40, (20000,), generator=g).float()        # few distinct values: one column
     X[2, :100] = float("nan")
     b = fit_binning(X, np.zeros(3, np.int32), None, max_bins=1016)
-    if fine == "1":
-        # 4-column features first (each fills one aligned row word), then the rest
-        assert b.F_orig == 3 and list(b.vmap) == [0, 0, 0, 0, 2, 2, 2, 2, 1] and b.n_low == 0
-        assert list(T.fine_columns(b.vmap, b.iscat, b.F)) == [1] * 8 + [0]
-    else:
-        # every feature's first column leads (narrow view of levels with <= 256 adaptive bins), then the k = 2
-        # subsets (with the first: every other fine edge, the 512-bin levels), then the odd subsets
-        assert b.F_orig == 3 and list(b.vmap) == [0, 1, 2, 0, 2, 0, 0, 2, 2] and (b.n_low, b.n_mid) == (3, 5)
-        assert T.fine_columns(b.vmap, b.iscat, b.F) is None
+    # every feature's first column leads (narrow view of levels with <= 256 adaptive bins), then the k = 2
+    # subsets (with the first: every other fine edge, the 512-bin levels), then the odd subsets
+    assert b.F_orig == 3 and list(b.vmap) == [0, 1, 2, 0, 2, 0, 0, 2, 2] and (b.n_low, b.n_mid) == (3, 5)
     # feature 0's columns in subset order k (column k holds e[k::4]: its first edge is fine edge k)
     c0 = sorted((int(j) for j in np.nonzero(b.vmap == 0)[0]), key=lambda j: float(b.edges[j][0]))
     c2 = [int(j) for j in np.nonzero(b.vmap == 2)[0]]
@@ -659,15 +649,13 @@ def test_narrow_levels_search_only_first_columns():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("fine", ["0", "1"])
 @pytest.mark.parametrize("case", ["plain", "kcols_adaptive", "newton", "narrow_planar", "kcols_adaptive_range",
                                   "narrow_planar_range"])
-def test_gpu_wide_bins_match_reference(case, fine, monkeypatch):
+def test_gpu_wide_bins_match_reference(case):
     """1016-bin numeric features (4 engine columns each) on the GPU engine vs RefTreeBuilder: identical
-    decisions, left weights and leaf assignment, including grouped column sampling (k_split_reduce fgroup), with and
-    without the fine-bin atomics of the 4-column groups (H2O_HIST_FINE, its aligned layout), and the narrow levels
-    of the default layout (adaptive cases: first columns only from level 2; planar: the routes move one plane)."""
-    monkeypatch.setenv("H2O_HIST_FINE", fine)
+    decisions, left weights and leaf assignment, including grouped column sampling (k_split_reduce fgroup), and the
+    narrow levels of the three-tier layout (adaptive cases: first columns only from level 2; planar: the routes move
+    one plane and level 1 reads the root split's direction bytes)."""
     X, y, info = _data(N=30000, F=10 if case.startswith("narrow_planar") else 6, cat=True, seed=11)
     if case.endswith("_range"):
         X = X.clone()
@@ -688,15 +676,11 @@ def test_gpu_wide_bins_match_reference(case, fine, monkeypatch):
     elif case.startswith("narrow_planar"):
         assert b.stride >= 64
         p = T.SplitParams(min_w=10, adapt_nbins=20, adapt_top=1024, edges=_edge_tab(b), vrange=vr)
-    elif case == "newton":           # unpacked two-plane histograms through the fine-bin atomics
+    elif case == "newton":           # unpacked two-plane histograms
         h = torch.full_like(y, 0.25)
         aux = torch.stack([h, -g, -g, h], 1).contiguous()
         p = T.SplitParams(min_w=1.0, lam=1.0, mode=T.MODE_NEWTON)
-    if fine == "1":
-        nnum = X.shape[0] - 1
-        assert T.fine_columns(b.vmap, b.iscat, b.F).sum() == 4 * nnum   # numeric features of 4 aligned columns
-    else:
-        assert b.n_low == X.shape[0]
+    assert b.n_low == X.shape[0]
     ref = T.RefTreeBuilder(bins, b.F, b.nbins, b.iscat, None, 5, p)
     ref.set_feature_groups(b.vmap, b.n_low, b.n_mid)
     ref.build(aux, None, k_cols, seed=5, leaf_fn=lambda ls: (ls[:, 0] / ls[:, 1]).float())
