@@ -10,8 +10,10 @@ length is normalised by the training min/max, ``predict = (max - len) / (max - m
 
 Extended Isolation Forest uses random hyperplanes (``extension_level`` non-zero normal components),
 so it cannot reuse axis-aligned histograms: trees are grown from the 256-row sample on the host
-(tiny) and scored on device by projecting all rows on every node normal with one GEMM per tree
-and walking the levels with gathers. Score ``s = 2^(-E[h(x)] / c(sample_size))``.
+(tiny) and scored on device by ``k_eif_path`` (``ops/eif.py``, ``csrc/eif_kernels.hip``): a lane per row walks
+every tree and takes an ordered fp64 dot product over the non-zero normal components of each node it visits;
+CPU tensors project all rows on every node normal with one GEMM per tree and walk the levels with gathers.
+Score ``s = 2^(-E[h(x)] / c(sample_size))``.
 """
 from __future__ import annotations
 
@@ -21,6 +23,7 @@ import numpy as np
 import torch
 
 from .. import metrics as mm
+from ..ops import eif as E
 from ..ops import tree as T
 from ..parallel import collectives as coll
 from .base import DataInfo, Model, make_key
@@ -171,25 +174,16 @@ class ExtendedIsolationForestModel(Model):
     def prediction_names(self):
         return ["anomaly_score", "mean_length"]
 
+    def _packed_forest(self):
+        """``ops.eif.pack`` of the trees, zeros of the normals dropped (the inputs are made finite first); packed
+        again when trees were added or restored since."""
+        pk = getattr(self, "_packed", None)
+        if pk is None or pk[0] is not self.trees or pk[1]["n_trees"] != len(self.trees):
+            pk = self._packed = (self.trees, E.pack(self.trees, keep_zeros=False))
+        return pk[1]
+
     def _path_lengths(self, X):
-        Xr = torch.nan_to_num(X.T.double(), nan=0.0)
-        N = Xr.shape[0]
-        tot = torch.zeros(N, dtype=torch.float64, device=Xr.device)
-        for tr in self.trees:
-            nrm = torch.as_tensor(tr["normal"], device=Xr.device)          # [nodes, F]
-            off = torch.as_tensor(tr["offset"], device=Xr.device)          # [nodes]
-            left = torch.as_tensor(tr["left"], device=Xr.device).long()
-            right = torch.as_tensor(tr["right"], device=Xr.device).long()
-            leafv = torch.as_tensor(tr["value"], device=Xr.device)
-            proj = Xr @ nrm.T - off                                         # one GEMM per tree
-            node = torch.zeros(N, dtype=torch.long, device=Xr.device)
-            for _ in range(int(tr["depth"]) + 1):
-                isleaf = left[node] < 0
-                go_left = proj.gather(1, node[:, None]).squeeze(1) <= 0
-                nxt = torch.where(go_left, left[node], right[node])
-                node = torch.where(isleaf, node, nxt)
-            tot += leafv[node]
-        return tot / max(1, len(self.trees))
+        return E.path_length_sums(X, self._packed_forest(), nan_to_zero=True) / max(1, len(self.trees))
 
     def _predict_tensor(self, X, offset=None):
         h = self._path_lengths(X)

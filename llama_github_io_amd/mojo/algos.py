@@ -395,25 +395,12 @@ def load_eif(ki, files):
 
 def score_eif(st, X):
     from ..models.isoforest import c_factor
-    Xr = X.T.double()
-    N = Xr.shape[0]
-    dev = Xr.device
-    tot = torch.zeros(N, dtype=torch.float64, device=dev)
-    for tr in st["trees"]:
-        nrm, pt = tr["normal"].to(dev), tr["point"].to(dev)
-        left, right, rows = tr["left"].to(dev), tr["right"].to(dev), tr["rows"].to(dev)
-        proj = Xr @ nrm.T - (nrm * pt).sum(1)            # (row - p) . n per node
-        node = torch.zeros(N, dtype=torch.long, device=dev)
-        height = torch.zeros(N, dtype=torch.float64, device=dev)
-        for _ in range(64):
-            isleaf = left[node] < 0
-            if bool(isleaf.all()):
-                break
-            go_left = proj.gather(1, node[:, None]).squeeze(1) <= 0     # NaN -> right, as in scoreTree0
-            node = torch.where(isleaf, node, torch.where(go_left, left[node], right[node]))
-            height = height + (~isleaf).double()
-        cf = torch.tensor([float(c_factor(int(r))) for r in tr["rows"].tolist()], dtype=torch.float64, device=dev)
-        tot += height + cf[node]
+    from ..ops import eif as E
+    if "_packed" not in st:
+        # every component listed, zeros too: a NaN or an infinity in a feature outside the hyperplane still
+        # poisons the projection and sends the row right, as in scoreTree0
+        st["_packed"] = E.pack(st["trees"], keep_zeros=True)
+    tot = E.path_length_sums(X, st["_packed"], nan_to_zero=False)
     h = tot / max(1, len(st["trees"]))
     c = float(c_factor(st["sample_size"]))
     return torch.stack([torch.pow(2.0, -h / c).float(), h.float()], 1)
