@@ -305,6 +305,14 @@ def metrics(mm: dict | None, category: str, model_id=None, frame_id=None, algo="
         out["centroid_stats"] = twodim("Centroid Statistics", [("centroid", "int", "%d"), ("size", "double", "%f"),
                                                                 ("within_cluster_sum_of_squares", "double", "%f")],
                                        [[i + 1, s, w] for i, (s, w) in enumerate(zip(sz, ws))])
+    elif cat == "BinomialUplift":
+        for k in ("auuc_table", "auuc_normalized_table", "auuc_random_table", "aecu_table"):
+            out[k] = _json_value(mm.get(k))
+        thr = mm.get("thresholds_and_metric_scores") or []
+        tcols = list(thr[0]) if thr else []
+        out["thresholds_and_metric_scores"] = twodim(
+            "Metrics for Thresholds", [(c, "double", "%f") for c in tcols] + [("idx", "int", "%d")],
+            [[r[c] for c in tcols] + [i] for i, r in enumerate(thr)])
     return out
 
 

@@ -273,15 +273,31 @@ class ModelMetrics(dict):
     def tied_y(self): return self.get("tied_y")
     def mean_score(self): return self.get("mean_score")
     def mean_normalized_score(self): return self.get("mean_normalized_score")
-    def auuc(self, metric=None): return self.get("AUUC")
-    def auuc_normalized(self, metric=None): return self.get("auuc_normalized")
+    # uplift (models/uplift.py auuc): ``metric`` is qini, lift or gain; None / AUTO = the model's auuc_type
+    def _uplift_kind(self, metric):
+        kind = str(metric or "AUTO").lower()
+        kind = self.get("auuc_type", "qini") if kind == "auto" else kind
+        if kind not in ("qini", "lift", "gain"):
+            raise ValueError(f"metric must be AUTO, qini, lift or gain, got {metric!r}")
+        return kind
+
+    def _uplift_column(self, name):
+        rows = self.get("thresholds_and_metric_scores")
+        return [r[name] for r in rows] if rows and name in rows[0] else None
+
+    def auuc(self, metric=None): return self.get(self._uplift_kind(metric)) if metric else self.get("AUUC")
+    def auuc_normalized(self, metric=None): return (self.get("auuc_normalized_table") or {}).get(self._uplift_kind(metric))
     def qini(self): return self.get("qini")
-    def aecu(self, metric="qini"): return (self.get("aecu_table") or {}).get(metric, self.get("aecu"))
+    def aecu(self, metric="qini"): return (self.get("aecu_table") or {}).get(self._uplift_kind(metric), self.get("aecu"))
     def auuc_table(self): return self.get("auuc_table")
     def aecu_table(self): return self.get("aecu_table")
-    def uplift(self, metric="AUTO"): return (self.get("auuc_table") or {}).get("uplift")
-    def uplift_normalized(self, metric="AUTO"): return (self.get("auuc_table") or {}).get("uplift_normalized")
-    def uplift_random(self, metric="AUTO"): return (self.get("auuc_table") or {}).get("uplift_random")
+    def uplift(self, metric="AUTO"): return self._uplift_column(self._uplift_kind(metric))
+    def uplift_normalized(self, metric="AUTO"): return self._uplift_column(self._uplift_kind(metric) + "_normalized")
+    def uplift_random(self, metric="AUTO"): return self._uplift_column(self._uplift_kind(metric) + "_random")
+    def ate(self): return self.get("ate")
+    def att(self): return self.get("att")
+    def atc(self): return self.get("atc")
+    def thresholds_and_metric_scores(self): return self.get("thresholds_and_metric_scores")
     def multinomial_auc_table(self): return self.get("multinomial_auc_table")
     def multinomial_aucpr_table(self): return self.get("multinomial_aucpr_table")
 

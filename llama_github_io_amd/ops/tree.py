@@ -1,4 +1,5 @@
-"""Histogram tree engine (device side) shared by GBM / DRF / XGBoost / IsolationForest / DT / Uplift.
+"""Histogram tree engine (device side) shared by GBM / DRF / XGBoost / IsolationForest / DT (Uplift DRF shares
+the binning and ``NA_BIN``; its level kernels are ``ops/uplift.py``).
 
 Two interchangeable builders produce the same :class:`TreeLevels` result:
 
